@@ -1,7 +1,7 @@
 """bench.py -- BASELINE.json's metric on MI355X: whole-job TFLOP/s (algorithmic n^3/3) of the recursive Cholesky
 with inverse (cholesky::cholinv<...>::factor) at n = 65536, inputs resident in HBM, at 1/2/4/8 GPUs of one node.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 either arrives launched (torch.distributed.run / mpiexec style: RANK, LOCAL_RANK, WORLD_SIZE, MASTER_* in the environment,
 one rank per GPU) or, when WORLD_SIZE is unset, starts its own N ranks the way `mpiexec -n P ./cholinv` starts the reference's bench
@@ -11,15 +11,25 @@ propagates the first non-zero exit and ends the remaining ranks; it refuses at o
 One "step" = one factor() call on the reference's synthetic SPD matrix (distribute_symmetric, structure.hpp:68-103).
 The matrix is the metric's own, n = 65536, at EVERY N (strong scaling): N = 1 holds it on one GPU (it fits: 139 GiB with
 both factors and the packed copies), N = 8 is BASELINE config 4 (2 x 2 x 2 grid).
-The same JSON line also carries
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, K timed steps, the outputs when asked for,
+the JSON line.  Its line carries
+  * `roofline`: the dominant kernel (the k-contiguous "TN" 128-tile MFMA kernel that runs the trailing update and the R12
+    product): every launch of it inside the timed region stamps its own execution interval (wall clock, first workgroup's start ..
+    last workgroup's end); achieved = algorithmic flops / union of those intervals (HIP-event brackets are reported beside it).
+--dump-outputs DIR writes what the last timed step computed, the arrays factor() hands its caller: DIR/R.npy and DIR/Rinv.npy
+(float64; N > 1: R_rank<r>.npy ... per rank), the local rows of R and R^-1 -- all of them when both fit DUMP_BYTES, else a fixed
+sample of rows drawn with DUMP_SEED (32 of 65536 at n = 65536 on one GPU).  The inputs are generated, so the same arguments give
+the same inputs on every run.
+
+--full measures and checks everything else as well, in the same process after the headline:
+  * `config.residual`: the reference validator on the headline's factors;
   * `config2`: n = 32768 on one GPU (BASELINE config 2), N = 1 only;
   * `cholesky_trsm_mode`: n = 65536 without forming any inverse (not the reference's schedule; an extra), at every N;
   * `cacqr2`: CA-CholeskyQR2 on m = 2^22 x 256 (BASELINE config 3), N = 1 only;
   * `cacqr2_config5`: CA-CholeskyQR2 with the per-GPU slice of BASELINE config 5, 2^23 x 1024 on every GPU (m = 2^23 N:
     weak in m; N = 8 IS config 5, m = 2^26), 4 m n^2 flops;
-  * `roofline`: the dominant kernel (the k-contiguous "TN" 128-tile MFMA kernel that runs the trailing update and the R12
-    product): every launch of it inside the timed region stamps its own execution interval (wall clock, first workgroup's start ..
-    last workgroup's end); achieved = algorithmic flops / union of those intervals (HIP-event brackets are reported beside it);
+  * `mfma_f64_loop_tflops`: a register-only MFMA loop, what the matrix pipe sustains on this device's clocks;
   * `cpu_baseline`: the reference's schedules on the node's own host BLAS (oracle.host_baseline, its own interpreter).
 """
 import argparse
@@ -42,6 +52,7 @@ if any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprofiler" 
         os.environ["ROC_AQL_QUEUE_SIZE"] = "131072"
         sys.stderr.write("bench.py: a rocprofiler tool is attached: ROC_AQL_QUEUE_SIZE=131072 (see profiles/r4_pmc_whole_bench_crash.txt)\n")
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -56,6 +67,8 @@ BASE_CASE_ORDER_ONE_GPU = 2048    # on one GPU: since round 4's work on the diag
                                   # between them; measured on one box each (profiles/r4_base_case_order_one_gpu.txt): n = 65536 1688.9 / 1689.0 -> 1683.3 / 1684.0 ms,
                                   # n = 32768 236.3-237.1 -> 235.4-235.8 ms; order 4096 and 512 lose
 T_START, BUDGET_S = 0.0, 480.0    # set in main()
+DUMP_BYTES = 32 << 20              # --dump-outputs: R and R^-1 together, at most
+DUMP_SEED = 65536                  # --dump-outputs: the rows of a sample
 
 
 def barrier_sync(distributed):
@@ -146,7 +159,16 @@ def leg_starts(tag):
         pass
 
 
-def time_cholesky(driver, L, h, n, c, bc, chunks, steps, warmup, distributed, device, bc_policy, trsm_mode=False, multipath=None):
+def output_sample(prob):
+    """R and R^-1 as factor() left them: all local rows when both fit DUMP_BYTES, else the same seeded sample of rows of each"""
+    k = min(prob.n_loc, max(1, DUMP_BYTES // (2 * 8 * prob.n_loc)))
+    rows = np.arange(prob.n_loc) if k == prob.n_loc else np.sort(np.random.default_rng(DUMP_SEED).choice(prob.n_loc, k, replace=False))
+    return {"R": prob.rows("R", rows), "Rinv": prob.rows("Rinv", rows)}
+
+
+def time_cholesky(driver, L, h, n, c, bc, chunks, steps, warmup, distributed, device, bc_policy, trsm_mode=False, multipath=None,
+                  check=True, outputs=False):
+    """W + K factor() calls, the last K timed; `check`: the residual of the last one (else None); `outputs`: its output_sample()"""
     leg_starts(f"cholesky n={n} grid c={c} chunks={chunks}" + (" TRSM mode" if trsm_mode else ""))
     if multipath is not None:          # read by topo::square when the grid object is built (capital_amd/src/util/topology.h)
         # "kslice": the replicated 2-GPU grid by K-slices + depth all-reduce instead of by output columns (summa.h: colsplit)
@@ -183,10 +205,11 @@ def time_cholesky(driver, L, h, n, c, bc, chunks, steps, warmup, distributed, de
         return {"launches": v[0].value, "union_ms": v[1].value, "sum_ms": v[2].value, "flops": v[3].value, "max_ms": v[4].value}
     iv, iv_tile, iv_pair, iva = intervals(103), intervals(11), intervals(27), intervals(-1)
     ms = dt / steps * 1e3
-    res = {"ms_per_step": ms, "tflops": n ** 3 / 3.0 / (ms * 1e-3) / 1e12, "residual": prob.residual(), "stats": prob.stats(),
+    res = {"ms_per_step": ms, "tflops": n ** 3 / 3.0 / (ms * 1e-3) / 1e12, "residual": prob.residual() if check else None, "stats": prob.stats(),
            "grid": [prob.d, prob.d, prob.c],
            "kernel": {"launches": launches.value, "ms": tot_ms.value, "flops": tot_fl.value, "max_ms": max_ms.value, "all_tile_ms": allv[1].value,
-                      "iv": iv, "iv_tile": iv_tile, "iv_pair": iv_pair, "iv_all": iva}}
+                      "iv": iv, "iv_tile": iv_tile, "iv_pair": iv_pair, "iv_all": iva},
+           "outputs": output_sample(prob) if outputs else None}
     prob.close()
     return res
 
@@ -270,7 +293,13 @@ def main():
     ap.add_argument("--qr-rows", type=int, default=0, help="override the rows per GPU of the config-5 slice (diagnostics / rehearsal only)")
     ap.add_argument("--one-device", action="store_true", help="rehearsal only: all N ranks on GPU 0 (needs CAPI_RCCL_LIB = the loopback "
                     "library of tests/rccl_loopback; RCCL itself refuses two ranks on one device); never a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write R and R^-1 of the last timed step (a fixed sample of rows when large) "
+                    "to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also the residual, the other configurations, the MFMA loop and the CPU "
+                    "baseline (--no-cpu / --no-qr / --no-config2 leave legs out)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus not in GRID_C:
         raise SystemExit(f"--gpus must be one of {sorted(GRID_C)} (d*d*c grids of one node)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -341,8 +370,10 @@ def main():
     if pinned:
         forms = [f for f in forms if f[0] == pinned] or forms[:1]
     name, chunks, mp = forms[0]
+    dump = bool(args.dump_outputs)
+    # one GPU: the residual is a --full check; N > 1: the choice of form below compares residuals
     r = time_cholesky(driver, L, h, n, c, bc, chunks, args.steps, args.warmup, distributed, device, bc_policy=0 if distributed else 2,
-                      multipath=mp if distributed else None)
+                      multipath=mp if distributed else None, check=args.full or distributed, outputs=dump)
     comm_forms = [{"form": name, "chunks": chunks, "multipath": mp, "ms_per_step": r["ms_per_step"], "residual": r["residual"], "timed": "full"}]
     if len(forms) > 1:
         import threading
@@ -426,7 +457,8 @@ def main():
             timer.daemon = True
             timer.start()
             try:
-                r = time_cholesky(driver, L, h, n, c, bc, chunks, args.steps, args.warmup, distributed, device, bc_policy=0, multipath=mp)
+                r = time_cholesky(driver, L, h, n, c, bc, chunks, args.steps, args.warmup, distributed, device, bc_policy=0, multipath=mp,
+                                  outputs=dump)
             finally:
                 barrier_sync(distributed)
                 timer.cancel()
@@ -438,6 +470,10 @@ def main():
                 comm_forms.append({"form": name, "note": "reported: the chosen form's full run did not validate or was not faster"})
     residual_max = max_over_ranks(r["residual"], distributed, device)
     out = make_line(args, n, bc, r, chunks, mp, rccl, residual_max, comm_forms if distributed else None, recorded_traffic(n, args.gpus))
+    if dump:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in r["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, f"{name}_rank{rank}.npy" if distributed else f"{name}.npy"), a)
     skipped = []
 
     def in_budget(what, est_s):
@@ -450,7 +486,7 @@ def main():
         return False
     step_s = r["ms_per_step"] * 1e-3
 
-    if args.gpus == 1 and not args.no_config2 and not args.n and in_budget("config2", 12 * step_s / 7 + 20):
+    if args.full and args.gpus == 1 and not args.no_config2 and not args.n and in_budget("config2", 12 * step_s / 7 + 20):
         n2 = 32768
         r2 = time_cholesky(driver, L, h, n2, 1, bc_mult_for(n2, 1, 1, BASE_CASE_ORDER_ONE_GPU), 0, max(args.steps, 3), 1, False, device, bc_policy=2)
         k2 = r2["kernel"]
@@ -461,14 +497,14 @@ def main():
         r2t = time_cholesky(driver, L, h, n2, 1, bc_mult_for(n2, 1, 1, BASE_CASE_ORDER_ONE_GPU), 0, max(args.steps, 3), 1, False, device, bc_policy=2, trsm_mode=True)
         out["config2"]["trsm_mode"] = {"tflops": r2t["tflops"], "ms_per_step": r2t["ms_per_step"], "residual": r2t["residual"]}
 
-    if args.gpus == 1 and not args.no_config2 and not args.n and in_budget("cholesky_trsm_mode", 4 * step_s + 15):
+    if args.full and args.gpus == 1 and not args.no_config2 and not args.n and in_budget("cholesky_trsm_mode", 4 * step_s + 15):
         # NOT the headline: the same matrix factored without forming any inverse (info::solve_with_trsm: potrf + block TRSM + SYRK,
         # what BASELINE north_star names; executes n^3/3 instead of the reference schedule's 5 n^3/12).  Same R, no R^-1.
         rt = time_cholesky(driver, L, h, n, 1, bc, 0, 2, 1, False, device, bc_policy=2, trsm_mode=True)
         out["cholesky_trsm_mode"] = {"workload": f"n={n} Cholesky, TRSM mode (R only, no inverse formed), 1 GPU", "tflops": rt["tflops"],
                                      "ms_per_step": rt["ms_per_step"], "residual": rt["residual"]}
 
-    if distributed and not args.no_config2 and not os.environ.get("CAPITAL_BENCH_NO_TRSM_GRID") and in_budget("cholesky_trsm_mode", 5 * step_s + 20):
+    if args.full and distributed and not args.no_config2 and not os.environ.get("CAPITAL_BENCH_NO_TRSM_GRID") and in_budget("cholesky_trsm_mode", 5 * step_s + 20):
         # NOT the headline: TRSM mode on the grid (cholinv.h: potrf_rec_grid; d == 1: every layer factors the replicated matrix) -- an extra;
         # its failure must not take the line with it (a driver error raises on every rank alike)
         try:
@@ -479,7 +515,7 @@ def main():
         except Exception as e:
             out["cholesky_trsm_mode"] = {"error": repr(e)[:300]}
 
-    if not args.no_qr and in_budget("cacqr2 / cacqr2_config5", 60):
+    if args.full and not args.no_qr and in_budget("cacqr2 / cacqr2_config5", 60):
         reps = max(args.steps, 3)
         if args.gpus == 1:
             m3, n3 = QR_CONFIG3
@@ -503,7 +539,7 @@ def main():
 
     if skipped:
         out["skipped_for_budget"] = {"budget_s": BUDGET_S, "legs": skipped}
-    if rank == 0:
+    if args.full and rank == 0:
         # register-only MFMA loop, two waves per SIMD, >= 100 ms: what the matrix pipe sustains on THIS device's clocks
         peak = C.c_double()
         L.capi_mfma_f64_peak(h, 250000, C.byref(peak))
@@ -511,7 +547,7 @@ def main():
     driver.finalize()
     if distributed:
         dist.destroy_process_group()
-    if rank == 0 and not args.no_cpu and args.gpus == 1:
+    if args.full and rank == 0 and not args.no_cpu and args.gpus == 1:
         out["cpu_baseline"] = cpu_baseline(16384, 1 << 18, 1024)      # ~25 s of host work on the box's CPU share
     if rank == 0:
         print(json.dumps(out), flush=True)

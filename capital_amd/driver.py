@@ -50,6 +50,7 @@ def bind(D):
     D.capital_cholinv_set_A.argtypes = [_vp, _dp]
     D.capital_cholinv_residual.argtypes = [_vp, _dp]
     D.capital_cholinv_get.argtypes = [_vp, _int, _dp]
+    D.capital_cholinv_get_rows.argtypes = [_vp, _int, _i64, C.POINTER(_i64), _dp]
     D.capital_cholinv_dims.argtypes = [_vp, C.POINTER(_i64)] + [C.POINTER(_int)] * 5
     D.capital_cholinv_stats.argtypes = [_vp] + [C.POINTER(_i64)] * 3
     D.capital_cholinv_set_trsm_mode.argtypes = [_vp, _int]
@@ -176,6 +177,14 @@ class Cholinv:
 
     def Rinv(self):
         return self._get(2)
+
+    def rows(self, which, rows):
+        """Local rows `rows` of R (which = 'R') or R^-1 ('Rinv') as a len(rows) x n_loc array -- a sample of a factor too large to fetch whole."""
+        idx = np.ascontiguousarray(rows, dtype=np.int64)
+        out = np.zeros((len(idx), self.n_loc), order="F")
+        _ck(self.D.capital_cholinv_get_rows(self.p, {"R": 1, "Rinv": 2}[which], len(idx), idx.ctypes.data_as(C.POINTER(_i64)),
+                                            out.ctypes.data_as(_dp)), "get_rows")
+        return out
 
     def stats(self):
         a, b, c_ = _i64(), _i64(), _i64()

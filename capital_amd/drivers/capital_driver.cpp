@@ -34,6 +34,7 @@ struct cholinv_problem {
   virtual void factor() = 0;
   virtual double residual() = 0;
   virtual void get(int which, double* host) = 0;
+  virtual void get_rows(int which, int64_t count, const int64_t* rows, double* host) = 0;
   virtual void dims(int64_t* nloc, int* x, int* y, int* z, int* d, int* c) = 0;
   virtual void stats(int64_t* bc, int64_t* levels, int64_t* bcdim) = 0;
   virtual void set_trsm_mode(bool on) = 0;
@@ -55,6 +56,20 @@ struct cholinv_impl : cholinv_problem {
     auto M = which == 1 ? Alg::construct_R(pack, grid) : Alg::construct_Rinv(pack, grid);
     auto v = M.to_host();
     std::memcpy(host, v.data(), sizeof(double) * v.size());
+  }
+  // local rows rows[0..count) of R (which = 1) or R^-1 (2), column-major count x n_loc: a sample of a factor that is too large
+  // to fetch whole (n = 65536 on one GPU: 32 GiB)
+  void get_rows(int which, int64_t count, const int64_t* rows, double* host) override {
+    if (which != 1 && which != 2) throw std::invalid_argument("cholinv get_rows: which must be 1 (R) or 2 (Rinv)");
+    auto M = which == 1 ? Alg::construct_R(pack, grid) : Alg::construct_Rinv(pack, grid);
+    const int64_t m = M.num_rows_local(), n = M.num_columns_local();
+    for (int64_t k = 0; k < count; ++k)
+      if (rows[k] < 0 || rows[k] >= m) throw std::invalid_argument("cholinv get_rows: row outside the local block");
+    if (count <= 0) return;
+    double* tmp = capital::dev_alloc(count * n);
+    for (int64_t k = 0; k < count; ++k) CAPITAL_CHECK(capi_dlacpy(capital::handle(), 0, 1, n, M.data() + rows[k], m, tmp + k, count));
+    CAPITAL_CHECK(capi_memcpy_d2h(capital::handle(), host, tmp, sizeof(double) * (size_t)(count * n)));
+    capital::dev_free(tmp);
   }
   void dims(int64_t* nloc, int* x, int* y, int* z, int* d, int* c) override {
     *nloc = A.num_rows_local(); *x = (int)grid.x; *y = (int)grid.y; *z = (int)grid.z; *d = (int)grid.d; *c = (int)grid.c;
@@ -177,6 +192,9 @@ int capital_cholinv_set_A(void* p, const double* host) { return guarded([&] { ((
 int capital_cholinv_factor(void* p) { return guarded([&] { ((cholinv_problem*)p)->factor(); }); }
 int capital_cholinv_residual(void* p, double* out) { return guarded([&] { *out = ((cholinv_problem*)p)->residual(); }); }
 int capital_cholinv_get(void* p, int which, double* host) { return guarded([&] { ((cholinv_problem*)p)->get(which, host); }); }
+int capital_cholinv_get_rows(void* p, int which, int64_t count, const int64_t* rows, double* host) {
+  return guarded([&] { ((cholinv_problem*)p)->get_rows(which, count, rows, host); });
+}
 int capital_cholinv_dims(void* p, int64_t* nloc, int* x, int* y, int* z, int* d, int* c) { return guarded([&] { ((cholinv_problem*)p)->dims(nloc, x, y, z, d, c); }); }
 int capital_cholinv_stats(void* p, int64_t* bc, int64_t* levels, int64_t* bcdim) { return guarded([&] { ((cholinv_problem*)p)->stats(bc, levels, bcdim); }); }
 // TRSM mode (info::solve_with_trsm): potrf + block TRSM + SYRK recursion, no inverse formed (one GPU, or a d x d x c grid: potrf_rec_grid)

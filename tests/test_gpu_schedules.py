@@ -96,6 +96,22 @@ def test_cholinv_repeat_is_deterministic(drv, oracle):
     p.close()
 
 
+def test_cholinv_row_sample_matches_the_whole_factors(drv):
+    """Cholinv.rows (the sample bench.py --dump-outputs writes) returns exactly the rows asked for, in their order, of R and R^-1"""
+    n = 1000
+    p = drv.Cholinv(n, bc_mult=-3, serialize=True)
+    p.generate()
+    p.factor()
+    R, Ri = p.R(), p.Rinv()
+    rows = [n - 1, 0, 517, 517, 3]
+    np.testing.assert_array_equal(p.rows("R", rows), R[rows])
+    np.testing.assert_array_equal(p.rows("Rinv", rows), Ri[rows])
+    for bad in ([n], [-1]):
+        with pytest.raises(drv.DriverError, match="outside the local block"):
+            p.rows("R", bad)
+    p.close()
+
+
 @pytest.mark.parametrize("serialize", (True, False))
 @pytest.mark.parametrize("m,n,variant", [(4096, 64, 2), (65536, 256, 2), (50001, 130, 2), (8192, 32, 1), (20000, 512, 2)])
 def test_cacqr_1d_matches_oracle(drv, oracle, m, n, variant, serialize):
