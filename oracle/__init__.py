@@ -80,6 +80,11 @@ def lib():
         L.orc_qr_residual.restype = _dbl
         L.orc_qr_orthogonality.argtypes = [_dp, _i64, _i64]
         L.orc_qr_orthogonality.restype = _dbl
+        L.orc_ld_cholesky_backward.argtypes = [_dp, _i64, _dp, _i64, _i64, _dp]
+        L.orc_ld_cholesky_probe.argtypes = [_dp, _i64, _dp, _i64, _i64, _dp, _i64, _dp]
+        L.orc_ld_inverse_residual.argtypes = [_dp, _i64, _dp, _i64, _i64, _int, _dp]
+        L.orc_ld_qr.argtypes = [_dp, _dp, _dp, _i64, _i64, _dp]
+        L.orc_ld_gemm_residual.argtypes = [_i64, _i64, _i64, _dp, _i64, _dp, _i64, _dbl, _dp, _i64, _dp]
         L.orc_set_threads.argtypes = [_int]
         L.orc_get_threads.restype = _int
         # OpenMP's default is one thread per hardware thread the affinity mask lists -- 128 on a one-GPU box whose cgroup share is 16 cores:
@@ -337,3 +342,51 @@ def qr_residual(A, Q, R):
 def qr_orthogonality(Q):
     Q = _f(Q)
     return lib().orc_qr_orthogonality(_p(Q), Q.shape[0], Q.shape[1])
+
+
+# ---- extended-precision validators (long double; not in the reference) ------------------------
+def ld_cholesky_backward(A, R):
+    """||A - R^T R||_F / ||A||_F in long double, reading only the upper triangles of A and R."""
+    A, R = _f(A), _f(R)
+    out = np.zeros(2)
+    lib().orc_ld_cholesky_backward(_p(A), A.shape[0], _p(R), R.shape[0], A.shape[0], _p(out))
+    return out[0] / out[1]
+
+
+def ld_cholesky_probe(A, R, k=4, seed=0):
+    """||(A - R^T R) V||_F / ||A V||_F with V = k seeded standard-normal columns, in long double (O(n^2 k))."""
+    A, R = _f(A), _f(R)
+    n = A.shape[0]
+    V = np.asfortranarray(np.random.default_rng(seed).standard_normal((n, k)))
+    out = np.zeros(2)
+    lib().orc_ld_cholesky_probe(_p(A), A.shape[0], _p(R), R.shape[0], n, _p(V), k, _p(out))
+    return out[0] / out[1]
+
+
+def ld_inverse_residual(X, R, side=0):
+    """X, R upper triangular (upper triangles only read).  side 0: (||X R - I||_F, || |X||R| ||_F);
+    side 1: (||R X - I||_F, || |R||X| ||_F).  Long double."""
+    X, R = _f(X), _f(R)
+    out = np.zeros(2)
+    lib().orc_ld_inverse_residual(_p(X), X.shape[0], _p(R), R.shape[0], X.shape[0], int(side), _p(out))
+    return out[0], out[1]
+
+
+def ld_qr(A, Q, R):
+    """(||Q^T Q - I||_F, ||A - Q R||_F / ||A||_F) in long double; only the upper triangle of R is read."""
+    A, Q, R = _f(A), _f(Q), _f(R)
+    m, n = A.shape
+    assert Q.shape == (m, n) and R.shape == (n, n)
+    out = np.zeros(3)
+    lib().orc_ld_qr(_p(A), _p(Q), _p(R), m, n, _p(out))
+    return out[0], out[1] / out[2]
+
+
+def ld_gemm_residual(A, B, alpha, Cm):
+    """(||A B - alpha C||_F, || |A||B| ||_F, ||alpha C||_F) in long double for dense A (m x k), B (k x n), C (m x n)."""
+    A, B, Cm = _f(A), _f(B), _f(Cm)
+    (m, k), n = A.shape, B.shape[1]
+    assert B.shape[0] == k and Cm.shape == (m, n)
+    out = np.zeros(3)
+    lib().orc_ld_gemm_residual(m, n, k, _p(A), A.shape[0], _p(B), B.shape[0], float(alpha), _p(Cm), Cm.shape[0], _p(out))
+    return out[0], out[1], out[2]

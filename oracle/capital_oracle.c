@@ -883,3 +883,144 @@ double orc_qr_orthogonality(const double* Q, int64_t m, int64_t n) {
   free(W);
   return sqrt(err) / sqrt(ctl);
 }
+
+/* ------------------------------------------------------------------------------------------
+ * Extended-precision validators (not in the reference).  All arithmetic in long double (x87
+ * 80-bit on x86-64, u = 2^-64): the residual's own rounding stays orders of magnitude below
+ * the n u effects of the fp64 result it checks.  Only the triangles named are read.
+ * ------------------------------------------------------------------------------------------ */
+/* out[0] = ||A - R^T R||_F, out[1] = ||A||_F over the full symmetric matrix; A and R: upper triangles only */
+void orc_ld_cholesky_backward(const double* A, int64_t lda, const double* R, int64_t ldr, int64_t n, double* out) {
+  long double err = 0.0L, ctl = 0.0L;
+#pragma omp parallel for schedule(dynamic, 4) reduction(+ : err, ctl)
+  for (int64_t j = 0; j < n; ++j) {
+    const double* rj = R + j * ldr;
+    for (int64_t i = 0; i <= j; ++i) {
+      const double* ri = R + i * ldr;
+      long double s = 0.0L;
+      for (int64_t k = 0; k <= i; ++k) s += (long double)ri[k] * (long double)rj[k];
+      const long double a = A[i + j * lda], d = a - s, w = i == j ? 1.0L : 2.0L;
+      err += w * d * d;
+      ctl += w * a * a;
+    }
+  }
+  out[0] = (double)sqrtl(err);
+  out[1] = (double)sqrtl(ctl);
+}
+
+/* Probe form: out[0] = ||(A - R^T R) V||_F, out[1] = ||A V||_F for V n x k (ld n); A, R: upper triangles only.  O(n^2 k). */
+void orc_ld_cholesky_probe(const double* A, int64_t lda, const double* R, int64_t ldr, int64_t n, const double* V, int64_t k,
+                           double* out) {
+  long double* W = (long double*)malloc(sizeof(long double) * n * k);
+  long double err = 0.0L, ctl = 0.0L;
+#pragma omp parallel for schedule(dynamic, 16)
+  for (int64_t i = 0; i < n; ++i)          /* W = R V: W_i = sum_{j >= i} R_ij V_j */
+    for (int64_t c = 0; c < k; ++c) {
+      long double s = 0.0L;
+      for (int64_t j = i; j < n; ++j) s += (long double)R[i + j * ldr] * (long double)V[j + c * n];
+      W[i + c * n] = s;
+    }
+#pragma omp parallel for schedule(dynamic, 16) reduction(+ : err, ctl)
+  for (int64_t i = 0; i < n; ++i)          /* row i of R^T W and of A V */
+    for (int64_t c = 0; c < k; ++c) {
+      long double y = 0.0L, av = 0.0L;
+      const double* ri = R + i * ldr;      /* column i of R: R_ji, j <= i */
+      for (int64_t j = 0; j <= i; ++j) y += (long double)ri[j] * W[j + c * n];
+      for (int64_t j = 0; j < n; ++j) {
+        const double a = j <= i ? A[j + i * lda] : A[i + j * lda];
+        av += (long double)a * (long double)V[j + c * n];
+      }
+      const long double d = av - y;
+      err += d * d;
+      ctl += av * av;
+    }
+  free(W);
+  out[0] = (double)sqrtl(err);
+  out[1] = (double)sqrtl(ctl);
+}
+
+/* X, R upper triangular (upper triangles only read).  side 0: E = X R - I, side 1: E = R X - I.
+ * out[0] = ||E||_F, out[1] = || |X| |R| ||_F (side 0) resp. || |R| |X| ||_F (side 1) */
+void orc_ld_inverse_residual(const double* X, int64_t ldx, const double* R, int64_t ldr, int64_t n, int side, double* out) {
+  const double* P = side ? R : X;
+  const double* Q = side ? X : R;
+  const int64_t ldp = side ? ldr : ldx, ldq = side ? ldx : ldr;
+  long double err = 0.0L, mag = 0.0L;
+#pragma omp parallel for schedule(dynamic, 4) reduction(+ : err, mag)
+  for (int64_t j = 0; j < n; ++j)
+    for (int64_t i = 0; i <= j; ++i) {
+      long double s = 0.0L, a = 0.0L;
+      for (int64_t k = i; k <= j; ++k) {
+        const long double t = (long double)P[i + k * ldp] * (long double)Q[k + j * ldq];
+        s += t;
+        a += fabsl(t);
+      }
+      if (i == j) s -= 1.0L;
+      err += s * s;
+      mag += a * a;
+    }
+  out[0] = (double)sqrtl(err);
+  out[1] = (double)sqrtl(mag);
+}
+
+/* out[0] = ||Q^T Q - I||_F, out[1] = ||A - Q R||_F, out[2] = ||A||_F; A, Q m x n (ld m), R n x n upper (upper triangle only read) */
+void orc_ld_qr(const double* A, const double* Q, const double* R, int64_t m, int64_t n, double* out) {
+  long double orth = 0.0L, err = 0.0L, ctl = 0.0L;
+#pragma omp parallel for schedule(dynamic, 1) reduction(+ : orth)
+  for (int64_t j = 0; j < n; ++j)
+    for (int64_t i = 0; i <= j; ++i) {
+      long double s = 0.0L;
+      const double *qi = Q + i * m, *qj = Q + j * m;
+      for (int64_t t = 0; t < m; ++t) s += (long double)qi[t] * (long double)qj[t];
+      if (i == j) s -= 1.0L;
+      orth += (i == j ? 1.0L : 2.0L) * s * s;
+    }
+#pragma omp parallel reduction(+ : err, ctl)
+  {
+    long double* acc = (long double*)malloc(sizeof(long double) * 256);
+#pragma omp for schedule(dynamic, 1)
+    for (int64_t r0 = 0; r0 < m; r0 += 256) {
+      const int64_t rb = MIN(256, m - r0);
+      for (int64_t j = 0; j < n; ++j) {
+        for (int64_t r = 0; r < rb; ++r) acc[r] = 0.0L;
+        for (int64_t k = 0; k <= j; ++k) {
+          const long double rk = R[k + j * n];
+          const double* qk = Q + k * m + r0;
+          for (int64_t r = 0; r < rb; ++r) acc[r] += (long double)qk[r] * rk;
+        }
+        for (int64_t r = 0; r < rb; ++r) {
+          const long double a = A[r0 + r + j * m], d = a - acc[r];
+          err += d * d;
+          ctl += a * a;
+        }
+      }
+    }
+    free(acc);
+  }
+  out[0] = (double)sqrtl(orth);
+  out[1] = (double)sqrtl(err);
+  out[2] = (double)sqrtl(ctl);
+}
+
+/* dense: out[0] = ||A B - alpha C||_F, out[1] = || |A| |B| ||_F, out[2] = ||alpha C||_F; A m x k, B k x n, C m x n */
+void orc_ld_gemm_residual(int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* B, int64_t ldb,
+                          double alpha, const double* Cm, int64_t ldc, double* out) {
+  long double err = 0.0L, mag = 0.0L, ctl = 0.0L;
+#pragma omp parallel for schedule(dynamic, 1) reduction(+ : err, mag, ctl)
+  for (int64_t j = 0; j < n; ++j)
+    for (int64_t i = 0; i < m; ++i) {
+      long double s = 0.0L, a = 0.0L;
+      for (int64_t t = 0; t < k; ++t) {
+        const long double p = (long double)A[i + t * lda] * (long double)B[t + j * ldb];
+        s += p;
+        a += fabsl(p);
+      }
+      const long double c = (long double)alpha * (long double)Cm[i + j * ldc], d = s - c;
+      err += d * d;
+      mag += a * a;
+      ctl += c * c;
+    }
+  out[0] = (double)sqrtl(err);
+  out[1] = (double)sqrtl(mag);
+  out[2] = (double)sqrtl(ctl);
+}

@@ -131,6 +131,20 @@ double orc_cholesky_residual(const double* A, const double* R, int64_t n);
 double orc_qr_residual(const double* A, const double* Q, const double* R, int64_t m, int64_t n);
 double orc_qr_orthogonality(const double* Q, int64_t m, int64_t n);
 
+/* Extended-precision validators (not in the reference): long double arithmetic (80-bit on x86-64), for bounds at the n u level.
+ * orc_ld_cholesky_backward: out = {||A - R^T R||_F, ||A||_F}, upper triangles of A and R only.
+ * orc_ld_cholesky_probe:    out = {||(A - R^T R) V||_F, ||A V||_F}, V n x k (ld n): the same residual in O(n^2 k).
+ * orc_ld_inverse_residual:  X, R upper; side 0: out = {||X R - I||_F, || |X||R| ||_F}, side 1: {||R X - I||_F, || |R||X| ||_F}.
+ * orc_ld_qr:                out = {||Q^T Q - I||_F, ||A - Q R||_F, ||A||_F}; A, Q m x n (ld m), R upper n x n.
+ * orc_ld_gemm_residual:     out = {||A B - alpha C||_F, || |A||B| ||_F, ||alpha C||_F}; A m x k, B k x n, C m x n. */
+void orc_ld_cholesky_backward(const double* A, int64_t lda, const double* R, int64_t ldr, int64_t n, double* out);
+void orc_ld_cholesky_probe(const double* A, int64_t lda, const double* R, int64_t ldr, int64_t n, const double* V, int64_t k,
+                           double* out);
+void orc_ld_inverse_residual(const double* X, int64_t ldx, const double* R, int64_t ldr, int64_t n, int side, double* out);
+void orc_ld_qr(const double* A, const double* Q, const double* R, int64_t m, int64_t n, double* out);
+void orc_ld_gemm_residual(int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* B, int64_t ldb,
+                          double alpha, const double* Cm, int64_t ldc, double* out);
+
 #ifdef __cplusplus
 }
 #endif
