@@ -23,10 +23,11 @@
 // latency-bound levels), gram_ts_kernel and trmm_right_ts32_kernel (CholeskyQR2's tall-skinny Gram matrix and Q = A R^-1,
 // full-width workgroups that read the tall operand once), and launch_gemm, which picks between them with a makespan
 // model in CU-cycles.
-// Diagnostic environment switches (read once): CAPI_DEBUG_GEMM (print every choice), CAPI_FORCE_TS=64|128, CAPI_SMALL=0|1,
-// CAPI_NO_TS, CAPI_TS_ROWS16, CAPI_NO_SHARE, CAPI_NO_SKIP, CAPI_NO_ROTATE, CAPI_NO_TAIL, CAPI_THIN_ROUNDS, CAPI_PEAK_BLOCKS_PER_CU,
-// CAPI_TILE_ORDER=0, CAPI_TRMM_PAIR=0|2, CAPI_ROUNDS=1, CAPI_PROF_DUMP.
+// launch_gemm plans (gemm_plan.h: plain C++, checked on the CPU by tests/gemm_plan) and launches what the plan says.
+// Diagnostic environment switches (read once): CAPI_DEBUG_GEMM (print every plan), CAPI_FORCE_TS=64|128, CAPI_SMALL=0|1,
+// CAPI_NO_SKIP, CAPI_PEAK_BLOCKS_PER_CU, CAPI_PROF_DUMP; the handle's launch modes: CAPI_ROUNDS, CAPI_TRMM_PAIR* (capi_core.hip).
 #include "capi_internal.h"
+#include "gemm_plan.h"
 #include <type_traits>
 
 extern "C" int capi_internal_copy2d(capi_handle_t h, int64_t m, int64_t n, const double* A, int64_t lda, double* B, int64_t ldb);   // movement.hip
@@ -36,8 +37,8 @@ typedef double d2_t __attribute__((ext_vector_type(2)));
 
 namespace {
 
-constexpr int BK = 16, NTHREADS = 256;
-constexpr int SK = BK + 2;            // [row][k] layout: row stride in doubles (144 B, 16-B aligned, odd multiple of 16 B)
+constexpr int NTHREADS = 256;
+using gemm_plan::BK, gemm_plan::SK;   // 16-deep k-panels; [row][k] layout: row stride in doubles (144 B, 16-B aligned, odd multiple of 16 B)
 // Two tile sizes share the code: TS = 128 (4x4 MFMA tiles per wave) for large outputs, TS = 64 (2x2 per wave, 4
 // workgroups per CU) when a 128-tiling would leave CUs idle (the small levels of the recursion).
 template <int TS> struct tile_cfg {
@@ -882,7 +883,7 @@ typedef void (*gemm_kernel_t)(const GemmArgs);
 // workgroup issues every load of a 256-deep chunk of both operand panels before anything else (32 x 16 bytes in flight
 // per thread), stages them through LDS in four 64-deep quarters as they land, and its four waves multiply one 16 x 16
 // MFMA tile each -- one exposed memory latency per 256 of K instead of one per 16, and 16x more workgroups per output.
-constexpr int ST = 32, SKC = 256, SQK = 64, SLD = ST + 2;
+using gemm_plan::ST, gemm_plan::SKC, gemm_plan::SQK, gemm_plan::SLD;    // 32-tiles, 256-deep chunks, 64-deep quarters, LDS row stride 34
 
 // Issue only: unconditional 16-byte loads from clamped addresses.  Everything that depends on the loaded values (edge
 // fix-ups, the triangle mask) lives in small_fix, called right before the quarter is staged -- a load inside a branch makes
@@ -1061,7 +1062,8 @@ gemm_kernel_t pick_small(bool ak, bool bkc) {
 // With n this small a square tiling re-reads the tall operand once per tile column (Gram: 3 x 128-tiles = 3 passes over
 // 8.6 GB, Q = A R^-1 with 64-tiles: 2.5 passes) and that, not the matrix pipe, sets the time.  Here one workgroup of 8
 // waves covers the FULL width, so every element of the tall operand travels global -> LDS exactly once.
-constexpr int TSK_THREADS = 512, TSK_W = 256;    // up to 16 column strips of 16
+constexpr int TSK_THREADS = 512;
+using gemm_plan::TSK_W;                           // 256: 16 column strips of 16
 // the tall operands are read once and written once: non-temporal accesses (CAPI_TS_NT=0 compiles the plain ones, A/B)
 #ifndef CAPI_TS_NT
 #define CAPI_TS_NT 1
@@ -1246,136 +1248,14 @@ __global__ __launch_bounds__(TSK_THREADS, 1) void gram_ts_kernel(const GemmArgs 
 
 // Q = alpha * A * T (+ beta * C) for a tall A (M x 256, row-contiguous) and a 256 x 256 UPPER triangular T.
 // T-stationary: wave w of the 8 keeps the MFMA fragments of output strips w and 15-w (16 columns each; 4 (w+1) + 4 (16-w)
-// = 68 k-steps, the same for every wave) in registers for the whole kernel.  A streams through LDS in 16-row tiles
-// (32 KB, read from HBM exactly once, two tiles in flight in registers beyond the one being multiplied); per tile a wave
-// reads each A fragment once and issues its 68 MFMAs with no barrier in between; each wave stores its own two strips.
-// Work per tile is uniform, so the one barrier per tile (8704 MFMA cycles) costs what it costs in the Gram kernel.
+// = 68 k-steps, the same for every wave) in registers for the whole kernel.  A streams through LDS in 32-row tiles (two
+// 16-row halves, each laid out [k][16 rows], 2 x 64 KB), read from HBM exactly once: every T fragment feeds two MFMAs, a wave
+// runs four accumulator chains, there is one barrier per 136 MFMAs, and a tile's 256 bytes of one column (= one address
+// translation; the 256 columns are 256 pages 8 lda bytes apart) are fetched by one 16-lane group.  One tile is in flight in
+// registers (its loads have the 136 MFMAs of the current tile to land); each wave stores its own two strips.
 // (A row-split variant that staged T's panels through LDS instead spent its time on T reloads, on short late panels and
-//  on `s_waitcnt vmcnt(0)` forced by mixing outstanding stores and loads: 8-9.6 ms against 7.6 ms for the tile kernel.)
-template <int W>
-__device__ __forceinline__ void trmm_ts_body(const GemmArgs& p, double* __restrict__ lds) {
-  constexpr int SA = W, SB = 15 - W, NA = 4 * (SA + 1), NB = 4 * (SB + 1);   // strips and their k-step counts (NA <= NB)
-  constexpr int TILE = 256 * 16;                           // LDS tile [k][16 rows]
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int r16 = lane & 15, g = lane >> 4;
-  const int ntile = (p.M + 15) >> 4;
-  // stationary T fragments: k-step s supplies T[4 s + g][16 strip + r16] (zero below the diagonal, unit diagonal on request)
-  double ta[NA], tb[NB];
-  auto tget = [&](int k, int j) {
-    double v = p.B[k + (int64_t)j * p.ldb];
-    if (k > j) v = 0.0;
-    if (p.tri_unit && k == j) v = 1.0;
-    return v;
-  };
-#pragma unroll
-  for (int s_ = 0; s_ < NA; ++s_) ta[s_] = tget(4 * s_ + g, 16 * SA + r16);
-#pragma unroll
-  for (int s_ = 0; s_ < NB; ++s_) tb[s_] = tget(4 * s_ + g, 16 * SB + r16);
-
-  // A tile -> registers: thread t owns rows 2 (t & 7), +1 of columns (t >> 3) + 64 q: the 8 lanes of a group fetch one
-  // whole 128-byte line (the tile's 16 rows of one column), a wave instruction 8 whole lines.  (A first mapping gave each
-  // thread 64 contiguous bytes: every instruction then touched 32 lines, 32 bytes of each, four times over.)
-  const int lc = tid >> 3, lr = 2 * (tid & 7);
-  auto load = [&](int tile, d2_t (&st)[4]) {
-    const bool in = 16 * tile + 16 <= p.M && p.a_vec;
-    const double* src = in ? p.A + 16 * tile + lr + (int64_t)lc * p.lda : p.A;
-    const int64_t cs = in ? 64 * p.lda : 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) st[q] = *(const d2_t*)(src + q * cs);
-  };
-  auto stage = [&](double* L, int tile, const d2_t (&st)[4]) {
-    // workgroup-uniform fast path: no branch (and so no conservative s_waitcnt vmcnt(0) at a join) around the LDS stores
-    if (p.a_vec && 16 * tile + 16 <= p.M) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) *(d2_t*)&L[(lc + 64 * q) * 16 + lr] = st[q];
-      return;
-    }
-    const int r = 16 * tile + lr;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {                           // ragged last tile / unaligned A: scalar reads
-      const int64_t c = lc + 64 * q;
-      d2_t v = {0.0, 0.0};
-      if (r < p.M) v.x = p.A[r + c * p.lda];
-      if (r + 1 < p.M) v.y = p.A[r + 1 + c * p.lda];
-      *(d2_t*)&L[c * 16 + lr] = v;
-    }
-  };
-  const int t0 = blockIdx.x, dt = gridDim.x;
-  if (t0 >= ntile) return;
-  d2_t stA[4], stB[4];
-  int par = 0;
-  // STEADY: the two tiles ahead exist and are full, A is 16-byte aligned and beta == 0 -- the iteration then has no branch
-  // at all.  That matters beyond the branch itself: a load or store inside a branch makes the compiler wait with
-  // s_waitcnt vmcnt(0) at the next use of ANY loaded value, i.e. each staging waited for the prefetch issued 68 MFMAs
-  // earlier AND for the previous tile's eight stores (measured: stores 1.8 ms, loads 1.3 ms of a 6.3 ms kernel whose
-  // MFMAs take 4.1 ms).  Straight-line, the wait before staging is vmcnt(12): stores and the newest prefetch stay in flight.
-  auto step = [&](int tile, d2_t (&cur)[4], d2_t (&nw)[4], auto steady_tag) {   // cur holds tile + dt, nw receives tile + 2 dt
-    constexpr bool STEADY = decltype(steady_tag)::value;
-    const double* L = lds + par * TILE;
-    if (STEADY) {
-      const double* src = p.A + 16 * (tile + 2 * dt) + lr + (int64_t)lc * p.lda;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) nw[q] = *(const d2_t*)(src + q * 64 * p.lda);
-    } else if (tile + 2 * dt < ntile) load(tile + 2 * dt, nw);
-    d4_t ca = {0.0, 0.0, 0.0, 0.0}, cb = {0.0, 0.0, 0.0, 0.0};
-    const double* la = L + g * 16 + r16;                    // A[row r16][k = 4 s + g]
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int s_ = 0; s_ < NB; ++s_) {
-      const double af = la[64 * s_];
-      if (s_ < NA) ca = __builtin_amdgcn_mfma_f64_16x16x4f64(ta[s_], af, ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f64_16x16x4f64(tb[s_], af, cb, 0, 0, 0);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    if (STEADY) {
-      double* Ln = lds + (par ^ 1) * TILE;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) *(d2_t*)&Ln[(lc + 64 * q) * 16 + lr] = cur[q];
-    } else if (tile + dt < ntile) stage(lds + (par ^ 1) * TILE, tile + dt, cur);
-    par ^= 1;
-    __syncthreads();
-    // lane holds (i = row r16 of the tile, j = 16 strip + g + 4 reg): 16 lanes -> 128 contiguous bytes of one column
-    // (beta is tested ONCE: a per-store `if (beta != 0) r += beta * *c` puts a load in a branch before every store, and
-    //  the compiler then parks an s_waitcnt vmcnt(0) at each join -- eight full drains of the prefetch queue per tile)
-    const int i = 16 * tile + r16;
-    if (STEADY || i < p.M) {
-      double* c0_ = p.C + i + (int64_t)(16 * SA + g) * p.ldc;
-      double* c1_ = p.C + i + (int64_t)(16 * SB + g) * p.ldc;
-      const int64_t s4 = 4 * p.ldc;
-      if (STEADY || p.beta == 0.0) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) { c0_[reg * s4] = p.alpha * ca[reg]; c1_[reg * s4] = p.alpha * cb[reg]; }
-      } else {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          c0_[reg * s4] = p.alpha * ca[reg] + p.beta * c0_[reg * s4];
-          c1_[reg * s4] = p.alpha * cb[reg] + p.beta * c1_[reg * s4];
-        }
-      }
-    }
-  };
-  load(t0, stA);
-  if (t0 + dt < ntile) load(t0 + dt, stB);
-  stage(lds, t0, stA);
-  __syncthreads();
-  int tile = t0;
-  if (p.a_vec && p.beta == 0.0) {
-    const int nfull = p.M >> 4;                             // tiles with all 16 rows
-    for (; tile + 3 * dt < nfull; tile += 2 * dt) {         // both steps see tile + 2 dt full
-      step(tile, stB, stA, std::true_type{});
-      step(tile + dt, stA, stB, std::true_type{});
-    }
-  }
-  for (; tile < ntile; tile += 2 * dt) {
-    step(tile, stB, stA, std::false_type{});
-    if (tile + dt < ntile) step(tile + dt, stA, stB, std::false_type{});
-  }
-}
-
-// The same T-stationary scheme on 32-row tiles (two 16-row halves, each laid out [k][16 rows] in LDS, 2 x 64 KB): every T
-// fragment feeds two MFMAs, a wave runs four accumulator chains instead of two, there is one barrier per 136 MFMAs, and a
-// tile's 256 bytes of one column (= one address translation; the 256 columns are 256 pages 8 lda bytes apart) are fetched
-// by one 16-lane group.  One tile is in flight in registers (its loads have the 136 MFMAs of the current tile to land).
+//  on `s_waitcnt vmcnt(0)` forced by mixing outstanding stores and loads: 8-9.6 ms against 7.6 ms for the tile kernel.  A
+//  16-row-tile form of this kernel, two tiles in flight, was measured and dropped for this one.)
 template <int W>
 __device__ __forceinline__ void trmm_ts32_body(const GemmArgs& p, double* __restrict__ lds) {
   constexpr int SA = W, SB = 15 - W, NA = 4 * (SA + 1), NB = 4 * (SB + 1);   // strips and their k-step counts (NA <= NB)
@@ -1534,281 +1414,32 @@ __global__ __launch_bounds__(TSK_THREADS, 1) void trmm_right_ts32_kernel(const G
 //  LDS image read with one ds_read_b128 per k-step; parity-green, 254 VGPRs, no spills, and 5.55 / 5.26 / 5.30 / 4.96 ms against 4.90 / 4.64 /
 //  4.83 / 4.46 for the register-staged kernel above (cm->cm / cm->p32 / p32->cm / p32->p32, same process order, min = median to 1 %:
 //  profiles/r3h_ts32_dma_ab.log).  With the stores compiled out the register kernel runs at 64.8 TFLOP/s, its MFMA work alone takes 4.1 ms.)
-__global__ __launch_bounds__(TSK_THREADS, 1) void trmm_right_ts_kernel(const GemmArgs p) {   // N == K == 256
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {
-    case 0: trmm_ts_body<0>(p, lds); break;
-    case 1: trmm_ts_body<1>(p, lds); break;
-    case 2: trmm_ts_body<2>(p, lds); break;
-    case 3: trmm_ts_body<3>(p, lds); break;
-    case 4: trmm_ts_body<4>(p, lds); break;
-    case 5: trmm_ts_body<5>(p, lds); break;
-    case 6: trmm_ts_body<6>(p, lds); break;
-    default: trmm_ts_body<7>(p, lds); break;
-  }
-}
-
 template <int TS>
 gemm_kernel_t pick_kernel(bool ak, bool bkc) {
   return ak ? (bkc ? dgemm_tile_kernel<TS, true, true> : dgemm_tile_kernel<TS, true, false>)
             : (bkc ? dgemm_tile_kernel<TS, false, true> : dgemm_tile_kernel<TS, false, false>);
 }
 
-int64_t count_tiles(const GemmArgs& p, int ts) {
-  const int64_t tm = cdiv(p.M, ts), tn = cdiv(p.N, ts);
-  return p.out_uplo < 0 ? tm * tn : tm * (tm + 1) / 2;
+// the environment switches the dispatcher honours, read once per process (the handle's launch modes: capi_core.hip)
+struct GemmEnv {
+  bool debug;                  // CAPI_DEBUG_GEMM: print every plan
+  int no_skip;                 // CAPI_NO_SKIP: the tile kernel never skips zero sub-tiles
+  gemm_plan::Overrides ov;     // CAPI_FORCE_TS, CAPI_SMALL
+};
+const GemmEnv& gemm_env() {
+  static const GemmEnv e = [] {
+    const char* fts = getenv("CAPI_FORCE_TS");
+    const char* fsm = getenv("CAPI_SMALL");
+    return GemmEnv{getenv("CAPI_DEBUG_GEMM") != nullptr, getenv("CAPI_NO_SKIP") ? 1 : 0, {fts ? atoi(fts) : 0, fsm ? (atoi(fsm) != 0) : -1}};
+  }();
+  return e;
 }
 
-// ws_for_slab: split-K partials go to the handle's primary workspace; callers that already stage through it
-// (in-place trmm) pass false.
-int launch_gemm(capi_handle_t h, bool ak, bool bkc, GemmArgs& p, bool ws_for_slab) {
-  if (p.M <= 0 || p.N <= 0) return CAPI_OK;
-  hipStream_t s = h->stream;
-  if (p.K <= 0 || p.alpha == 0.0) {
-    if (p.beta == 1.0) return CAPI_OK;
-    dim3 grid((unsigned)cdiv(p.M, 256), (unsigned)(p.N < 65535 ? p.N : 65535));
-    hipLaunchKernelGGL(scale_kernel, grid, dim3(256), 0, s, p.C, p.ldc, p.M, p.N, p.beta, p.out_uplo);
-    CAPI_HIP_CHECK(h, hipGetLastError());
-    return CAPI_OK;
-  }
-  // tall-skinny right-TRMM (Q = A R^-1): persistent full-width workgroups, A read once
-  {
-    static const bool no_ts2 = getenv("CAPI_NO_TS") != nullptr;
-    if (!no_ts2 && p.tri_side == CAPI_RIGHT && p.tri_eff_upper && !ak && bkc && p.N == TSK_W && p.K == p.N &&
-        (int64_t)p.M >= 64 * (int64_t)p.N) {
-      p.a_vec = (((uintptr_t)p.A & 15) == 0) && ((p.lda & 1) == 0);
-      p.splitk = 1;
-      static const bool rows16 = getenv("CAPI_TS_ROWS16") != nullptr;     // the 16-row-tile variant (A/B)
-      CAPI_REQUIRE(h, !(rows16 && (p.a_tiled || p.c_tiled)), "panel32 images need the 32-row T-stationary kernel");
-      const int rows = rows16 ? 16 : 32;
-      const int ntile = (int)cdiv(p.M, rows);
-      const int grid = ntile < h->num_cu ? ntile : h->num_cu;
-      const size_t lds_bytes = sizeof(double) * 2 * 256 * rows;
-      void (*k)(const GemmArgs) = rows16 ? trmm_right_ts_kernel : trmm_right_ts32_kernel;
-      CAPI_RAISE_LDS_LIMIT(h, rows16 ? CAPI_ATTR_TRMM_TS16 : CAPI_ATTR_TRMM_TS32, k, lds_bytes);
-      hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(TSK_THREADS), lds_bytes, s, p);
-      CAPI_HIP_CHECK(h, hipGetLastError());
-      return CAPI_OK;
-    }
-  }
-  // Tall-skinny Gram matrix WIDER than the full-width kernel (CholeskyQR2 at n = 512..2048; config 5: n = 1024, K = 2^23): by 256-blocks.
-  // The 128-tiling computes its diagonal tiles whole (36 tile-units for 32 at n = 1024: 11 % of the MFMAs produce the unwanted
-  // triangle).  Here the diagonal 256-blocks go to the full-width kernel below, whose 136-of-256 tile map wastes 6 % of a quarter
-  // of the work, and the off-diagonal blocks are plain 256 x 256 products A_I^T A_J on the tile kernel (split-K; the four tiles of a
-  // slice are consecutive arrivals on one XCD and share their panels in its L2).  (CAPI_NO_TALL: the plain 128-tiling, A/B.)
-  {
-    static const bool no_tall_gram = getenv("CAPI_NO_TALL") != nullptr || getenv("CAPI_NO_TS") != nullptr;
-    if (!no_tall_gram && p.out_uplo == CAPI_UPPER && p.tri_side < 0 && ak && bkc && p.A == p.B && p.lda == p.ldb && p.N > TSK_W &&
-        p.N <= 2048 && p.N % TSK_W == 0 && (int64_t)p.K >= 64 * (int64_t)p.N && ws_for_slab && p.batch <= 1) {
-      const int nb = p.N / TSK_W;
-      for (int J = 0; J < nb; ++J)
-        for (int I = 0; I <= J; ++I) {
-          GemmArgs q = p;
-          q.A = p.A + (int64_t)I * TSK_W * p.lda;
-          q.B = p.A + (int64_t)J * TSK_W * p.lda;
-          q.C = p.C + (int64_t)I * TSK_W + (int64_t)J * TSK_W * p.ldc;
-          q.M = q.N = TSK_W;
-          q.out_uplo = I == J ? CAPI_UPPER : -1;
-          int rc = launch_gemm(h, true, true, q, true);
-          if (rc != CAPI_OK) return rc;
-        }
-      return CAPI_OK;
-    }
-  }
-  // tall-skinny Gram matrix: full-width workgroups, the tall operand is read once
-  {
-    static const bool no_ts = getenv("CAPI_NO_TS") != nullptr;
-    if (!no_ts && p.out_uplo == CAPI_UPPER && p.tri_side < 0 && ak && bkc && p.A == p.B && p.lda == p.ldb && p.N <= TSK_W &&
-        p.N >= 64 && (int64_t)p.K >= 64 * (int64_t)p.N && ws_for_slab) {
-      const int64_t P = cdiv(p.K, BK);
-      int S = (int)(P / 32 < h->num_cu ? (P / 32 > 0 ? P / 32 : 1) : h->num_cu);       // one resident workgroup per CU
-      p.a_vec = (((uintptr_t)p.A & 15) == 0) && ((p.lda & 1) == 0);
-      p.splitk = S;
-      p.slab = nullptr; p.slab_ld = p.N; p.slab_stride = (int64_t)p.N * p.N;
-      if (S > 1) {
-        void* ws;
-        int rc = capi_ws_get(h, sizeof(double) * (size_t)p.slab_stride * (size_t)S, &ws);
-        if (rc != CAPI_OK) return rc;
-        p.slab = (double*)ws;
-      }
-      const size_t lds_bytes = sizeof(double) * 2 * TSK_W * SK;
-      CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_GRAM_TS, gram_ts_kernel, lds_bytes);
-      hipLaunchKernelGGL(gram_ts_kernel, dim3((unsigned)S), dim3(TSK_THREADS), lds_bytes, s, p);
-      CAPI_HIP_CHECK(h, hipGetLastError());
-      if (S >= 16 && p.N <= 65535) {
-        hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3((unsigned)cdiv(p.M, 64), (unsigned)p.N), dim3(256), 0, s, p.slab, p.slab_ld,
-                           p.slab_stride, p.splitk, p.C, p.ldc, p.M, p.N, p.alpha, p.beta, p.out_uplo);
-        CAPI_HIP_CHECK(h, hipGetLastError());
-      } else if (S > 1) {
-        dim3 grid((unsigned)cdiv(p.M, 256), (unsigned)(p.N < 65535 ? p.N : 65535));
-        hipLaunchKernelGGL(splitk_reduce_kernel, grid, dim3(256), 0, s, p.slab, p.slab_ld, p.slab_stride, p.splitk, p.C, p.ldc,
-                           p.M, p.N, p.alpha, p.beta, p.out_uplo);
-        CAPI_HIP_CHECK(h, hipGetLastError());
-      }
-      return CAPI_OK;
-    }
-  }
-  // (panel32 images are understood by the two full-width tall-skinny kernels above and by nothing below: the entry points check the switches that
-  //  could route such an operand here -- CAPI_NO_TS, CAPI_TS_ROWS16 -- per call, the dispatch above reads them once per process, so a process that
-  //  changes them between calls must get a refusal, not a tile kernel that reads an image as column-major with ld 32)
-  CAPI_REQUIRE(h, !p.a_tiled && !p.c_tiled, "panel32 operand reached a kernel that does not read it");
-  // Choose tile size and split-K from a small cost model in CU-cycles.  One k-panel (16 deep) of a 128-tile keeps all
-  // four MFMA pipes of a CU busy for 64 MFMAs x 64 cycles = 4096 cycles, of a 64-tile for 1024; co-resident workgroups
-  // share the pipes, so a CU works through the tiles dealt to it at that rate whatever their number.  The makespan is
-  // the busiest CU's queue: ceil(tiles / CUs) equal tiles, or for TRMM (k-range grows linearly along the triangular
-  // dimension, longest-first dealing) the larger of the mean load and the single longest tile.
-  const bool tri = p.tri_side >= 0;
-  const double ghz = 2.35;
-  double best = 1e300;
-  int best_ts = 128, best_s = 1;
-  static const char* force_ts = getenv("CAPI_FORCE_TS");
-  for (int ts : {128, 64}) {
-    if (force_ts && atoi(force_ts) != ts) continue;
-    const double nt = (double)count_tiles(p, ts);
-    const double cyc = ts == 128 ? 4096.0 : 1024.0;
-    const double eff = ts == 128 ? 0.89 : 0.80;          // measured pipe utilisation of the two kernels (fast path)
-    const int ncu = h->cu_of[h->cur] ? h->cu_of[h->cur] : h->num_cu;
-    for (int sk = 1; sk <= 512; ++sk) {
-      if (sk > 1 && (!ws_for_slab || p.K / sk < 256)) break;
-      double busiest;                                     // cycles of work queued on the busiest CU
-      if (!tri) {
-        // a CU keeps `res` workgroups resident; the last, partially filled group of its queue runs without partners to
-        // cover its barrier and load stalls (measured ~0.7x the paired rate for a lone 128-tile workgroup)
-        const int64_t q = cdiv((int64_t)nt * sk, ncu);
-        const int res = ts == 128 ? 2 : 4;
-        const int64_t lone = q % res;
-        const double per = ((double)p.K / sk / 16.0) * cyc;
-        busiest = (double)(q - lone) * per + (double)lone * per / (lone == 0 ? 1.0 : (0.62 + 0.38 * (double)lone / res));
-      } else {
-        const double kmax = (double)p.K / sk, kavg = (0.5 * p.K + 0.5 * ts) / sk;
-        const double mean = nt * sk * (kavg / 16.0) * cyc / ncu, longest = (kmax / 16.0) * cyc;
-        busiest = mean * 1.08 > longest ? mean * 1.08 : longest;
-      }
-      double t = busiest / (ghz * 1e3 * eff) + 7.0;
-      // operand panels stream from L2/MALL: ~4 TB/s effective when every tile re-reads its two panels
-      // (a syrk's diagonal tiles stage one panel; a TRMM's triangular operand is small and stays cache resident)
-      const double keff = tri ? 0.5 * p.K + 0.5 * ts : (double)p.K;
-      const double panels = (p.out_uplo >= 0 && p.A == p.B) ? 2.0 * nt - (double)cdiv(p.N, ts) : (tri ? 1.0 * nt : 2.0 * nt);
-      // (operands that fit the 256 MB Infinity Cache are re-read from there at roughly twice the HBM-side rate)
-      const double footprint = ((p.A == p.B ? 0.0 : (double)p.M) + (double)p.N) * (double)p.K * 8.0;
-      double t_mem = panels * ts * keff * 8.0 / (footprint <= 192.0e6 ? 8.0e6 : 4.0e6);
-      // a split-K slice whose tiles all fit one XCD's resident set (<= 32 tiles: consecutive pids, started together, walking the
-      // same panels in step) shares those panels in that L2: a tall product then streams each operand about once
-      if (!tri && nt <= 32.0 && (double)p.K >= 64.0 * (double)(p.M > p.N ? p.M : p.N)) t_mem = footprint / 4.0e6;
-      if (t_mem > t) t = t_mem;
-      if (sk > 1) t = 1.12 * t + 6.0 + (double)(sk + 2) * (double)p.M * (double)p.N * (p.out_uplo >= 0 ? 0.5 : 1.0) * 8.0 / 2.5e6;
-      if (t < best) { best = t; best_ts = ts; best_s = sk; }
-    }
-  }
-  static const bool dbg = getenv("CAPI_DEBUG_GEMM") != nullptr;
-  if (dbg) fprintf(stderr, "[capi gemm] M=%d N=%d K=%d uplo=%d tri=%d -> ts=%d splitk=%d est=%.1f us\n", p.M, p.N, p.K, p.out_uplo, p.tri_side, best_ts, best_s, best);
-  // latency-bound sizes go to the burst-load 32-tile kernel: one workgroup per CU (139 KB of LDS), per 256-deep chunk
-  // ~2 us of exposed load latency + 64 MFMAs per wave
-  {
-    static const char* force_small = getenv("CAPI_SMALL");
-    const double nt32 = (double)cdiv(p.M, ST) * (double)cdiv(p.N, ST) * (p.out_uplo >= 0 ? 0.5 : 1.0);
-    const double keff = tri ? 0.5 * p.K + 16.0 : (double)p.K;
-    const double chunks = keff / SKC < 1.0 ? 1.0 : keff / SKC;
-    const double t_small = (double)cdiv((int64_t)nt32, h->num_cu) * (chunks * 2.0 + keff * (16.0 / 2200.0) * 4.0 / 4.0) + 3.0;
-    bool use_small = p.M <= 512 && p.N <= 512 && p.K <= 2048;      // measured: 1.5-2x faster up to order 512, slower from 1024
-    // thin products of the blocked factorization (K <= 256: a 128-row panel against up to ~2000 columns, its trailing
-    // update): one staged chunk, LDS sized by K, so two workgroups share a CU at K <= 128
-    static const int thin_rounds = getenv("CAPI_THIN_ROUNDS") ? atoi(getenv("CAPI_THIN_ROUNDS")) : 3;
-    if (!use_small && p.K <= SKC && p.batch <= 1) {
-      const double slots = (double)h->num_cu * (p.K <= 128 ? 2.0 : 1.0);
-      use_small = nt32 <= thin_rounds * slots;
-    }
-    if (force_small) use_small = atoi(force_small) != 0 && p.M <= 4096 && p.N <= 4096;
-    if (dbg) fprintf(stderr, "[capi gemm]   small-kernel estimate %.1f us -> %s\n", t_small, use_small ? "small" : "tile");
-    if (use_small) {
-      const int kcap = p.K >= SKC ? SKC : (int)(cdiv(p.K, SQK) * SQK);      // staged depth: LDS holds 2 x kcap x SLD doubles
-      p.ts = kcap;
-      p.tiles_m = (int)cdiv(p.M, ST);
-      p.tiles_n = (int)cdiv(p.N, ST);
-      p.ntiles = p.tiles_m * p.tiles_n;
-      p.a_vec = (((uintptr_t)p.A & 15) == 0) && ((p.lda & 1) == 0);
-      p.b_vec = (((uintptr_t)p.B & 15) == 0) && ((p.ldb & 1) == 0);
-      p.splitk = 1;
-      gemm_kernel_t k = pick_small(ak, bkc);
-      const size_t lds_bytes = sizeof(double) * 2 * (size_t)kcap * SLD;
-      const int vi = (ak ? 2 : 0) + (bkc ? 1 : 0);
-      CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_SMALL0 + vi, k, sizeof(double) * 2 * SKC * SLD);
-      if (dbg) {
-        static long launch_no = 0;
-        fprintf(stderr, "[capi gemm]   small launch #%ld v=%d grid=(%d,%d) lds=%zu stream=%p A=%p lda=%ld B=%p ldb=%ld C=%p ldc=%ld batch=%d sa=%ld sb=%ld sc=%ld\n",
-                ++launch_no, vi, p.ntiles, p.batch > 1 ? p.batch : 1, lds_bytes, (void*)s, (const void*)p.A, (long)p.lda, (const void*)p.B, (long)p.ldb,
-                (void*)p.C, (long)p.ldc, p.batch, (long)p.sa, (long)p.sb, (long)p.sc);
-      }
-      hipLaunchKernelGGL(k, dim3((unsigned)p.ntiles, (unsigned)(p.batch > 1 ? p.batch : 1)), dim3(256), lds_bytes, s, p);
-      CAPI_HIP_CHECK(h, hipGetLastError());
-      return CAPI_OK;
-    }
-  }
-  p.ts = best_ts;
-  p.tiles_m = (int)cdiv(p.M, p.ts);
-  p.tiles_n = (int)cdiv(p.N, p.ts);
-  p.ntiles = (int)count_tiles(p, p.ts);
-  p.a_vec = (((uintptr_t)p.A & 15) == 0) && ((p.lda & 1) == 0);
-  p.b_vec = (((uintptr_t)p.B & 15) == 0) && ((p.ldb & 1) == 0);
-  p.no_skip = getenv("CAPI_NO_SKIP") ? 1 : 0;
-  p.share_ab = (p.out_uplo >= 0 && p.A == p.B && p.lda == p.ldb && ak == bkc && !getenv("CAPI_NO_SHARE")) ? 1 : 0;
-  {
-    static const int order_mode = getenv("CAPI_TILE_ORDER") ? atoi(getenv("CAPI_TILE_ORDER")) : 1;
-    static const int order_min = getenv("CAPI_TILE_ORDER_MIN") ? atoi(getenv("CAPI_TILE_ORDER_MIN")) : 16;
-    p.order = 0;
-    if (p.out_uplo >= 0 && (order_mode & 1) && p.tiles_n >= order_min) p.order |= 1;
-  }
-  p.splitk = 1;
-  p.k_per_split = p.K;
-  p.k_rotate = 0;
-  p.slab = nullptr;
-  p.slab_ld = p.slab_stride = 0;
-  if (best_s > 1) {
-    const int64_t kps = cdiv(cdiv(p.K, best_s), BK) * BK;
-    const int64_t sk = cdiv(p.K, kps);
-    if (sk > 1) {
-      p.splitk = (int)sk;
-      p.k_per_split = (int)kps;
-      p.k_rotate = (!tri && !getenv("CAPI_NO_ROTATE")) ? 1 : 0;
-      p.slab_ld = p.M;
-      p.slab_stride = (int64_t)p.M * p.N;
-      void* ws;
-      int rc = capi_ws_get(h, sizeof(double) * (size_t)p.slab_stride * (size_t)sk, &ws);
-      if (rc != CAPI_OK) return rc;
-      p.slab = (double*)ws;
-    }
-  }
-  // A 128-tiling fills the chip in rounds of 2 x CUs workgroups; the last round is usually partial and its lone
-  // workgroups run at ~0.6 of the paired rate (8256 tiles = 16 rounds + 64: those 64 cost almost another round).  The
-  // tail is re-cut into 64-tiles (4x the workgroups, a quarter of the length) and launched right behind the full rounds.
-  // (CAPI_ROUNDS_MIN_K: products shallower than this keep the handle's environment defaults -- one launch, pairs up to four whole rounds --
-  //  even while capi_set_launch_rounds is on: a round of a shallow product is short, and every boundary drains the chip once; A/B knob)
-  static const int rounds_min_k = getenv("CAPI_ROUNDS_MIN_K") ? atoi(getenv("CAPI_ROUNDS_MIN_K")) : 0;
-  const bool deep = p.K >= rounds_min_k;
-  const int rounds_mode = deep ? h->rounds_mode : h->rounds_env[0];
-  const int64_t per_round = 2 * (int64_t)(h->cu_of[h->cur] ? h->cu_of[h->cur] : h->num_cu);
-  // (bit 0: plain products; bit 1: triangular outputs in the banded order -- an XCD's 64 tiles of a round are an 8 x 8 block of the triangle)
-  // (the 256-column block launches of a tall right-TRMM were tried the same way: a round there is 512 tiles of K <= 1024, ~0.15 ms, and the
-  //  launch boundaries cost 11 %: 35.1 -> 39.2 ms at m = 2^21, n = 1024; r3s)
-  const bool use_rounds = p.ts == 128 && p.splitk == 1 && !tri && per_round % 16 == 0 && p.batch <= 1 && (int64_t)p.ntiles >= 2 * per_round &&
-                          (p.out_uplo < 0 ? (rounds_mode & 1) != 0 : ((rounds_mode & 2) != 0 && (p.order & 1)));      // (see "Resident rounds" below)
-  int tail128 = 0;
-  if (p.ts == 128 && p.splitk == 1 && !tri && !getenv("CAPI_NO_TAIL")) {
-    const int per_round = 2 * (h->cu_of[h->cur] ? h->cu_of[h->cur] : h->num_cu);
-    const int rem = p.ntiles % per_round;
-    if (p.ntiles >= 2 * per_round && rem > 0 && rem <= (3 * per_round) / 4) tail128 = rem;
-  }
-  const int ntiles_all = p.ntiles;
-  p.tail_base = 0; p.tail_tm = p.tail_tn = 0;
-  p.ntiles -= tail128;
-  gemm_kernel_t k = p.ts == 128 ? pick_kernel<128>(ak, bkc) : pick_kernel<64>(ak, bkc);
-  const size_t lds_bytes = sizeof(double) * 2 * (p.ts == 128 ? tile_cfg<128>::STAGE_LDS : tile_cfg<64>::STAGE_LDS);
-  const int64_t nblk = (int64_t)p.ntiles * p.splitk;
-  CAPI_REQUIRE(h, nblk < (int64_t)1 << 31, "too many tiles");
-  // HIP events around EVERY launch of the tile kernel (capi_prof_*): one record per launch, its share of the algorithmic flops
-  auto prof_open = [&](double share, capi_handle_s::prof_rec*& rec) -> int {
-    rec = nullptr;
-    if (!h->prof_on) return CAPI_OK;
+// One launch of the tile kernel or its pair form.  With capi_prof_* on it gets a record: HIP events around it, its `share` of the
+// product's algorithmic flops and its device-side interval (q.stamp), or no interval when the stamp pool is exhausted.
+int launch_recorded(capi_handle_t h, gemm_kernel_t k, int64_t grid, size_t lds_bytes, GemmArgs q, double share, int variant) {
+  capi_handle_s::prof_rec* rec = nullptr;
+  if (h->prof_on) {
     if (h->prof_n == h->prof_cap) {
       const int ncap = h->prof_cap ? h->prof_cap * 2 : 1024;
       auto* np_ = (capi_handle_s::prof_rec*)realloc(h->prof, sizeof(capi_handle_s::prof_rec) * ncap);
@@ -1821,118 +1452,155 @@ int launch_gemm(capi_handle_t h, bool ak, bool bkc, GemmArgs& p, bool ws_for_sla
     if (!rec->e0) { CAPI_HIP_CHECK(h, hipEventCreate(&rec->e0)); CAPI_HIP_CHECK(h, hipEventCreate(&rec->e1)); }
     // algorithmic flops of the whole product: gemm 2MNK, triangular output N(N+1)K, trmm M^2 N / M N^2
     // (a tri_block launch is one 256-column block of a tall right-TRMM: a dense product above T's diagonal block plus that block's triangle)
-    rec->flops = p.out_uplo >= 0 ? (double)p.N * ((double)p.N + 1.0) * (double)p.K
-                 : (p.tri_side >= 0 ? (p.tri_block ? (double)p.M * (double)p.N * (2.0 * (double)p.tri_koff + (double)p.N) : (double)p.M * (double)p.N * (double)p.K)
-                                    : 2.0 * (double)p.M * (double)p.N * (double)p.K);
+    rec->flops = q.out_uplo >= 0 ? (double)q.N * ((double)q.N + 1.0) * (double)q.K
+                 : (q.tri_side >= 0 ? (q.tri_block ? (double)q.M * (double)q.N * (2.0 * (double)q.tri_koff + (double)q.N) : (double)q.M * (double)q.N * (double)q.K)
+                                    : 2.0 * (double)q.M * (double)q.N * (double)q.K);
     rec->flops *= share;
-    rec->variant = (ak ? 2 : 0) + (bkc ? 1 : 0) + (p.ts == 128 ? 0 : 4);
-    rec->m = p.M; rec->n = p.N; rec->k = p.K; rec->kind = p.out_uplo >= 0 ? 1 : (p.tri_side >= 0 ? 2 : 0);
-    CAPI_HIP_CHECK(h, hipEventRecord(rec->e0, s));
-    return CAPI_OK;
-  };
-  // the launch's device-side interval record (capi_prof_collect_intervals), or null when profiling is off / the pool is exhausted
-  auto stamp_of = [&](const capi_handle_s::prof_rec* rec) -> unsigned long long* {
-    const int64_t idx = rec ? rec - h->prof : -1;
-    return (rec && h->d_stamps && idx < h->stamps_cap) ? h->d_stamps + 2 * idx : nullptr;
-  };
-  // Resident rounds (plain products).  A launch with more tiles than the chip holds (2 per CU) refills slots one by one as tiles
-  // finish: within a few tile lengths the starts are smeared and tiles that share an operand panel are no longer within the ~2
-  // iterations an XCD's 4 MiB L2 can bridge (its 64 resident tiles pull 2 MiB of panels through it per iteration).  One launch per
-  // round restarts every XCD's 64 tiles together, as an 8 x 8 block of the tile grid (tile_of_dims' bands): 16 panels serve 64
-  // tiles.  dgemm 16384^3: FETCH 139 -> 76 GB (the 8-way ideal is 69), time unchanged (118.7 vs 119.0 ms): the tiles of a plain
-  // product do equal work, so the round boundary costs nothing measurable.  Triangular outputs were tried the same way (8 x 8
-  // super-blocks of the triangle, 8 per round): FETCH of the n = 32768 step 310 -> 263 GB only, dsyrk 16384 62.6 -> 64.2 ms,
-  // step 237 -> 242 ms (partial rounds, diagonal super-blocks with 36 live tiles): not kept.  TRMM tiles have unequal k-ranges
-  // and keep the longest-first free-running order.  OFF by default (CAPI_ROUNDS=1 turns it on): inside cholinv the plain products
-  // are the lookahead's rectangles only -- the step's fabric traffic falls by 5 % (3625 -> 3437 GB at n = 65536), its time does
-  // not change, and the per-launch durations the roofline is computed from stretch, because the round launches of a low-priority
-  // bulk stream queue behind the chain's kernels at every boundary (0.876 -> 0.825 on the same box).
-  // TRMM in tile pairs (dtrmm_pair_kernel): equal work per workgroup, the launch of a plain product
-  {
-    const int pair_mode = deep ? h->pair_mode : h->rounds_env[1];
-    // Measured (tools/pair_window.py, all three forms of the recursion): a launch of exactly one resident round +8..10 % (order 4096:
-    // 63 -> 68.5 TFLOP/s; 2048 x 8192: 51..55 -> 55..59), two rounds +2..3 %, four +0.5..1 %, nine +-0.5 %; a launch that is NOT whole
-    // rounds loses (1152 workgroups, order 6144: 68.3 -> 61.5 -- the equal, long workgroups of the last 128 cost a third round).
-    // L2-to-fabric traffic does not change (order 32768: 2 x FETCH_SIZE 1.19 -> 1.22 TB).  Pairs therefore run up to four whole rounds
-    // (CAPI_TRMM_PAIR=2: whenever the launch is whole rounds; =0: never); larger products keep the longest-first order.
-    const int ntri_ = p.tri_side == CAPI_LEFT ? p.tiles_m : p.tiles_n, nfree_ = p.tri_side == CAPI_LEFT ? p.tiles_n : p.tiles_m;
-    const int64_t wgs = (int64_t)(ntri_ / 2) * nfree_;
-    const int pair_rounds = deep ? h->pair_rounds : h->rounds_env[2], pair_rounds_min = deep ? h->pair_rounds_min : h->rounds_env[3];
-    if (pair_mode && tri && !p.tri_dense && !p.tri_block && p.tri_koff == 0 && p.ts == 128 && p.splitk == 1 && p.beta == 0.0 && p.batch <= 1 &&
-        p.M % 128 == 0 && p.N % 128 == 0 && p.K % 128 == 0 && p.a_vec && p.b_vec && (ntri_ & 1) == 0 &&
-        wgs % per_round == 0 && (pair_mode > 1 || wgs <= 4 * per_round || (pair_rounds && p.K >= pair_rounds_min))) {
-      gemm_kernel_t kp = ak ? (bkc ? dtrmm_pair_kernel<true, true> : dtrmm_pair_kernel<true, false>)
-                            : (bkc ? dtrmm_pair_kernel<false, true> : dtrmm_pair_kernel<false, false>);
-      CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_PAIR0 + (ak ? 2 : 0) + (bkc ? 1 : 0), kp, lds_bytes);
-      // Pairs do equal work, so a launch can go out one resident round (512 workgroups: an 8 x 8 block of pair-tiles per XCD) at a time
-      // at no cost in time, and every round's tiles start -- and, walking equal k-ranges, stay -- together: the panels an XCD's 64 tiles
-      // share are fetched once instead of once per drifting tile (CAPI_TRMM_PAIR_ROUNDS; measured in round 3).
-      if (pair_rounds && wgs > per_round && p.K >= pair_rounds_min) {
-        for (int64_t base = 0; base < wgs; base += per_round) {
-          GemmArgs q = p;
-          q.pid_base = (int)base;
-          capi_handle_s::prof_rec* rec;
-          int rc = prof_open((double)per_round / (double)wgs, rec);
-          if (rc != CAPI_OK) return rc;
-          if (rec) rec->variant += 16;
-          q.stamp = stamp_of(rec);
-          hipLaunchKernelGGL(kp, dim3((unsigned)per_round), dim3(NTHREADS), lds_bytes, s, q);
-          if (rec) CAPI_HIP_CHECK(h, hipEventRecord(rec->e1, s));
-        }
-        CAPI_HIP_CHECK(h, hipGetLastError());
-        return CAPI_OK;
-      }
-      capi_handle_s::prof_rec* rec;
-      int rc = prof_open(1.0, rec);
-      if (rc != CAPI_OK) return rc;
-      if (rec) rec->variant += 16;                                      // its own kernel symbol: not counted with dgemm_tile_kernel's launches
-      p.stamp = stamp_of(rec);
-      hipLaunchKernelGGL(kp, dim3((unsigned)wgs), dim3(NTHREADS), lds_bytes, s, p);
-      if (rec) CAPI_HIP_CHECK(h, hipEventRecord(rec->e1, s));
-      CAPI_HIP_CHECK(h, hipGetLastError());
-      return CAPI_OK;
-    }
+    rec->variant = variant;
+    rec->m = q.M; rec->n = q.N; rec->k = q.K; rec->kind = q.out_uplo >= 0 ? 1 : (q.tri_side >= 0 ? 2 : 0);
+    CAPI_HIP_CHECK(h, hipEventRecord(rec->e0, h->stream));
+    const int64_t idx = rec - h->prof;
+    q.stamp = h->d_stamps && idx < h->stamps_cap ? h->d_stamps + 2 * idx : nullptr;
   }
-  if (use_rounds) {
-    for (int64_t base = 0; base < nblk; base += per_round) {
-      GemmArgs q = p;
-      q.pid_base = (int)base;
-      const int64_t cnt = nblk - base < per_round ? nblk - base : per_round;
-      capi_handle_s::prof_rec* rec;
-      int rc = prof_open((double)cnt / (double)ntiles_all, rec);
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NTHREADS), lds_bytes, h->stream, q);
+  if (rec) CAPI_HIP_CHECK(h, hipEventRecord(rec->e1, h->stream));
+  return CAPI_OK;
+}
+
+int launch_reduce(capi_handle_t h, const GemmArgs& p, gemm_plan::Reduce kind) {
+  if (kind == gemm_plan::Reduce::none) return CAPI_OK;
+  if (kind == gemm_plan::Reduce::wide)
+    hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3((unsigned)cdiv(p.M, 64), (unsigned)p.N), dim3(256), 0, h->stream, p.slab, p.slab_ld,
+                       p.slab_stride, p.splitk, p.C, p.ldc, p.M, p.N, p.alpha, p.beta, p.out_uplo);
+  else
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)cdiv(p.M, 256), (unsigned)(p.N < 65535 ? p.N : 65535)), dim3(256), 0, h->stream,
+                       p.slab, p.slab_ld, p.slab_stride, p.splitk, p.C, p.ldc, p.M, p.N, p.alpha, p.beta, p.out_uplo);
+  CAPI_HIP_CHECK(h, hipGetLastError());
+  return CAPI_OK;
+}
+
+// Plans the product (gemm_plan.h) and launches what the plan says.  ws_for_slab: split-K partials go to the handle's primary
+// workspace; callers that already stage through it (in-place trmm) pass false.
+int launch_gemm(capi_handle_t h, bool ak, bool bkc, GemmArgs& p, bool ws_for_slab) {
+  using gemm_plan::Path;
+  const GemmEnv& env = gemm_env();
+  gemm_plan::Product d;
+  d.M = p.M; d.N = p.N; d.K = p.K; d.out_uplo = p.out_uplo;
+  d.tri_side = p.tri_side; d.tri_eff_upper = p.tri_eff_upper; d.tri_dense = p.tri_dense; d.tri_block = p.tri_block; d.tri_koff = p.tri_koff;
+  d.alpha_zero = p.alpha == 0.0; d.beta = p.beta; d.batch = p.batch; d.ak = ak; d.bkc = bkc;
+  d.a_is_b = p.A == p.B; d.same_ld = p.lda == p.ldb;
+  d.a_vec = (((uintptr_t)p.A & 15) == 0) && ((p.lda & 1) == 0);
+  d.b_vec = (((uintptr_t)p.B & 15) == 0) && ((p.ldb & 1) == 0);
+  d.a_tiled = p.a_tiled; d.c_tiled = p.c_tiled; d.ws_for_slab = ws_for_slab;
+  const gemm_plan::Device dev{h->num_cu, h->cu_of[h->cur]};
+  const gemm_plan::Modes modes{h->rounds_mode, h->pair_mode, h->pair_rounds, h->pair_rounds_min};
+  const gemm_plan::Plan pl = gemm_plan::plan(d, dev, modes, env.ov);
+  if (env.debug) {
+    char line[2048];
+    gemm_plan::format(line, sizeof(line), d, dev, modes, env.ov, pl);
+    fprintf(stderr, "[capi gemm] %s\n", line);
+  }
+  hipStream_t s = h->stream;
+  if (pl.path == Path::none) return CAPI_OK;
+  CAPI_REQUIRE(h, pl.path != Path::refused, "panel32 operand reached a kernel that does not read it");
+  if (pl.path == Path::scale) {
+    dim3 grid((unsigned)cdiv(p.M, 256), (unsigned)(p.N < 65535 ? p.N : 65535));
+    hipLaunchKernelGGL(scale_kernel, grid, dim3(256), 0, s, p.C, p.ldc, p.M, p.N, p.beta, p.out_uplo);
+    CAPI_HIP_CHECK(h, hipGetLastError());
+    return CAPI_OK;
+  }
+  if (pl.path == Path::trmm_ts32) {
+    p.a_vec = d.a_vec;
+    p.splitk = 1;
+    CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_TRMM_TS32, trmm_right_ts32_kernel, pl.lds_bytes);
+    hipLaunchKernelGGL(trmm_right_ts32_kernel, dim3((unsigned)pl.blocks), dim3(TSK_THREADS), pl.lds_bytes, s, p);
+    CAPI_HIP_CHECK(h, hipGetLastError());
+    return CAPI_OK;
+  }
+  if (pl.path == Path::gram_blocks) {          // diagonal blocks: the full-width Gram kernel; the others: 256 x 256 products A_I^T A_J
+    for (int J = 0; J < pl.tiles_n; ++J)
+      for (int I = 0; I <= J; ++I) {
+        GemmArgs q = p;
+        q.A = p.A + (int64_t)I * TSK_W * p.lda;
+        q.B = p.A + (int64_t)J * TSK_W * p.lda;
+        q.C = p.C + (int64_t)I * TSK_W + (int64_t)J * TSK_W * p.ldc;
+        q.M = q.N = TSK_W;
+        q.out_uplo = I == J ? CAPI_UPPER : -1;
+        int rc = launch_gemm(h, true, true, q, true);
+        if (rc != CAPI_OK) return rc;
+      }
+    return CAPI_OK;
+  }
+  if (pl.path == Path::gram_ts) {
+    p.a_vec = d.a_vec;
+    p.splitk = pl.splitk;
+    p.slab = nullptr; p.slab_ld = pl.slab_ld; p.slab_stride = pl.slab_stride;
+    if (pl.reduce != gemm_plan::Reduce::none) {
+      void* ws;
+      int rc = capi_ws_get(h, sizeof(double) * (size_t)p.slab_stride * (size_t)p.splitk, &ws);
       if (rc != CAPI_OK) return rc;
-      q.stamp = stamp_of(rec);
-      hipLaunchKernelGGL(k, dim3((unsigned)cnt), dim3(NTHREADS), lds_bytes, s, q);
-      if (rec) CAPI_HIP_CHECK(h, hipEventRecord(rec->e1, s));
+      p.slab = (double*)ws;
     }
-  } else {
-    capi_handle_s::prof_rec* rec;
-    int rc = prof_open((double)p.ntiles / (double)ntiles_all, rec);              // (the tail launch below is not part of this record)
+    CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_GRAM_TS, gram_ts_kernel, pl.lds_bytes);
+    hipLaunchKernelGGL(gram_ts_kernel, dim3((unsigned)pl.blocks), dim3(TSK_THREADS), pl.lds_bytes, s, p);
+    CAPI_HIP_CHECK(h, hipGetLastError());
+    return launch_reduce(h, p, pl.reduce);
+  }
+  p.ts = pl.ts;
+  p.tiles_m = pl.tiles_m;
+  p.tiles_n = pl.tiles_n;
+  p.ntiles = pl.ntiles;
+  p.a_vec = d.a_vec;
+  p.b_vec = d.b_vec;
+  if (pl.path == Path::small) {
+    p.splitk = 1;
+    gemm_kernel_t k = pick_small(ak, bkc);
+    CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_SMALL0 + pl.variant, k, sizeof(double) * 2 * SKC * SLD);
+    hipLaunchKernelGGL(k, dim3((unsigned)pl.blocks, (unsigned)pl.grid_y), dim3(256), pl.lds_bytes, s, p);
+    CAPI_HIP_CHECK(h, hipGetLastError());
+    return CAPI_OK;
+  }
+  // the tile kernel, or its pair form for TRMMs
+  p.no_skip = env.no_skip;
+  p.share_ab = pl.share_ab;
+  p.order = pl.order;
+  p.splitk = pl.splitk;
+  p.k_per_split = pl.k_per_split;
+  p.k_rotate = pl.k_rotate;
+  p.slab = nullptr; p.slab_ld = pl.slab_ld; p.slab_stride = pl.slab_stride;
+  p.tail_base = 0; p.tail_tm = p.tail_tn = 0;
+  CAPI_REQUIRE(h, pl.blocks < (int64_t)1 << 31, "too many tiles");
+  if (pl.splitk > 1) {
+    void* ws;
+    int rc = capi_ws_get(h, sizeof(double) * (size_t)p.slab_stride * (size_t)p.splitk, &ws);
     if (rc != CAPI_OK) return rc;
-    p.stamp = stamp_of(rec);
-    hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(NTHREADS), lds_bytes, s, p);
-    if (rec) CAPI_HIP_CHECK(h, hipEventRecord(rec->e1, s));
+    p.slab = (double*)ws;
+  }
+  gemm_kernel_t k = p.ts == 128 ? pick_kernel<128>(ak, bkc) : pick_kernel<64>(ak, bkc);
+  if (pl.path == Path::pair) {
+    k = ak ? (bkc ? dtrmm_pair_kernel<true, true> : dtrmm_pair_kernel<true, false>)
+           : (bkc ? dtrmm_pair_kernel<false, true> : dtrmm_pair_kernel<false, false>);
+    CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_PAIR0 + (ak ? 2 : 0) + (bkc ? 1 : 0), k, pl.lds_bytes);
+  }
+  for (int64_t i = 0; i < pl.launches(); ++i) {          // one launch, or one per resident round
+    GemmArgs q = p;
+    q.pid_base = (int)(i * pl.per_launch);
+    int rc = launch_recorded(h, k, pl.count(i), pl.lds_bytes, q, pl.share(i), pl.variant);
+    if (rc != CAPI_OK) return rc;
   }
   CAPI_HIP_CHECK(h, hipGetLastError());
-  if (tail128 > 0) {
+  if (pl.tail128 > 0) {                     // (neither in a record's flops nor in its interval)
     GemmArgs q = p;
     q.ts = 64;
-    q.stamp = nullptr;                      // (the tail is neither in the record's flops nor in its interval)
     q.tail_base = p.ntiles;                 // first 128-tile of the tail (p.ntiles > 0 here)
     q.tail_tm = p.tiles_m; q.tail_tn = p.tiles_n;
     q.tiles_m = (int)cdiv(p.M, 64); q.tiles_n = (int)cdiv(p.N, 64);
-    q.ntiles = 4 * tail128;
+    q.ntiles = 4 * pl.tail128;
     hipLaunchKernelGGL(pick_kernel<64>(ak, bkc), dim3((unsigned)q.ntiles), dim3(NTHREADS),
                        sizeof(double) * 2 * tile_cfg<64>::STAGE_LDS, s, q);
     CAPI_HIP_CHECK(h, hipGetLastError());
   }
-  if (p.splitk > 1) {
-    dim3 grid((unsigned)cdiv(p.M, 256), (unsigned)(p.N < 65535 ? p.N : 65535));
-    hipLaunchKernelGGL(splitk_reduce_kernel, grid, dim3(256), 0, s, p.slab, p.slab_ld, p.slab_stride, p.splitk, p.C, p.ldc,
-                       p.M, p.N, p.alpha, p.beta, p.out_uplo);
-    CAPI_HIP_CHECK(h, hipGetLastError());
-  }
-  return CAPI_OK;
+  return launch_reduce(h, p, pl.reduce);
 }
 
 bool ok01(int v) { return v == 0 || v == 1; }
@@ -2025,8 +1693,7 @@ static int trmm_launch(capi_handle_t h, int side, int uplo, int trans, int diag,
   // iterations at n = 1024.  Here T's triangle is copied ONCE into a zeroed n x n block of the handle (8 MiB at n = 1024, read
   // by every tile anyway) and the kernel is told the other triangle holds zeros: all iterations take the lean loop; the k-range
   // of a tile is still cut at its diagonal block, the other triangle of the CALLER's T is still never read.
-  static const bool no_tall = getenv("CAPI_NO_TALL") != nullptr;
-  if (!no_tall && side == CAPI_RIGHT && diag == CAPI_NONUNIT && n >= 512 && n <= 4096 && m >= 64 * n) {
+  if (side == CAPI_RIGHT && diag == CAPI_NONUNIT && n >= 512 && n <= 4096 && m >= 64 * n) {
     void* w;
     int rc = capi_ws3_get(h, sizeof(double) * (size_t)n * (size_t)n, &w);
     if (rc != CAPI_OK) return rc;
@@ -2041,8 +1708,7 @@ static int trmm_launch(capi_handle_t h, int side, int uplo, int trans, int diag,
     // n = 1024) stays in every L2 and its tiles have near-equal k-ranges: m = 2^23: 147.0 -> 142.5 ms, n = 512: 51.8 -> 56.6 TFLOP/s; block 0
     // (K = 256) is the T-stationary kernel's shape.  B is still fetched once per column tile (FETCH_SIZE unchanged): an XCD streams
     // 2 MiB of panels per iteration through its 4 MiB L2, so a partner tile one iteration behind already misses; making the two
-    // column tiles of a row tile consecutive arrivals was measured slower (152.7 ms).  (CAPI_TALL_ONE_LAUNCH: A/B.)
-    static const bool one_launch = getenv("CAPI_TALL_ONE_LAUNCH") != nullptr;
+    // column tiles of a row tile consecutive arrivals was measured slower (152.7 ms).
     const bool eff_upper = (uplo == CAPI_UPPER) != (trans == CAPI_TRANS);
     // (Round 3, measured and dropped: each block's diagonal 256 x 256 part by the T-stationary kernel -- exactly the 136 live MFMA tiles,
     //  B_J read once -- and the part above it as a dense beta = 1 product on the tile kernel: 16.25 instead of 18 executed units of
@@ -2052,7 +1718,7 @@ static int trmm_launch(capi_handle_t h, int side, int uplo, int trans, int diag,
     //  (44 % of those panels' MFMAs, wave-uniform branches, no masking needed on the clean copy): 141.4 / 141.9 against 141.4 / 141.7 ms at
     //  m = 2^23, n = 1024 -- nothing.  A panel costs what its busiest wave costs: the waves of the tile's right half keep all their columns until
     //  the last three panels, and the barrier makes the others wait for them.  profiles/r4_tall_trmm_band_skip_ab.txt.)
-    if (!one_launch && eff_upper && n % 256 == 0) {
+    if (eff_upper && n % 256 == 0) {
       for (int64_t J = 0; J < n / 256; ++J) {
         GemmArgs q = p;
         q.N = 256;
@@ -2086,7 +1752,7 @@ __attribute__((visibility("hidden"))) int capi_internal_trmm_oop_batched(capi_ha
                                                                            int64_t ldt, int64_t st, const double* B, int64_t ldb,
                                                                            int64_t sb_, double* C, int64_t ldc, int64_t sc_, int batch) {
   CAPI_REQUIRE(h, h && m >= 0 && n >= 0 && m < (1LL << 31) && n < (1LL << 31) && batch >= 0, "dims");      // (GemmArgs carries 32-bit extents)
-  const bool small_ok = m <= 512 && n <= 512 && !getenv("CAPI_SMALL");
+  const bool small_ok = m <= 512 && n <= 512 && gemm_env().ov.force_small < 0;
   const bool aligned = ((st | sb_ | sc_) & 1) == 0;      // keeps the 16-byte alignment decision valid for every batch member
   if (batch > 1 && small_ok && aligned) {
     const int64_t nt = side == CAPI_LEFT ? m : n;
@@ -2138,7 +1804,6 @@ int capi_dsyrk_panel32(capi_handle_t h, int64_t n, int64_t k, double alpha, cons
   CAPI_REQUIRE(h, h, "null handle");
   CAPI_REQUIRE(h, n == TSK_W && k > 0 && k % 32 == 0 && k >= 64 * n && k < (1LL << 31), "panel32 Gram matrix: n == 256, k a multiple of 32, k >= 64 n");
   CAPI_REQUIRE(h, A32 && C && ldc >= n && (((uintptr_t)A32 & 15) == 0), "operands");
-  CAPI_REQUIRE(h, getenv("CAPI_NO_TS") == nullptr, "panel32 images need the full-width tall-skinny kernels (CAPI_NO_TS is set)");
   GemmArgs p{};
   p.A = A32; p.B = A32; p.C = C; p.lda = 32; p.ldb = 32; p.ldc = ldc;
   p.M = (int)n; p.N = (int)n; p.K = (int)k; p.alpha = alpha; p.beta = beta;
@@ -2153,7 +1818,6 @@ int capi_dtrmm_right_panel32(capi_handle_t h, int64_t m, int64_t n, double alpha
   CAPI_REQUIRE(h, h, "null handle");
   CAPI_REQUIRE(h, n == TSK_W && m > 0 && m % 32 == 0 && m >= 64 * n && m < (1LL << 31), "panel32 right-TRMM: n == 256, m a multiple of 32, m >= 64 n");
   CAPI_REQUIRE(h, T && B && C && ldt >= n && (ldb == 0 || ldb >= m) && (ldc == 0 || ldc >= m) && (const double*)C != B, "operands");
-  CAPI_REQUIRE(h, getenv("CAPI_NO_TS") == nullptr && getenv("CAPI_TS_ROWS16") == nullptr, "panel32 images need the 32-row T-stationary kernel");
   GemmArgs p{};
   p.C = C; p.ldc = ldc ? ldc : 32; p.M = (int)m; p.N = (int)n; p.K = (int)n; p.alpha = alpha; p.beta = 0.0;
   p.out_uplo = -1; p.tri_side = CAPI_RIGHT; p.tri_eff_upper = 1; p.tri_unit = 0;

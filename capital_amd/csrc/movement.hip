@@ -312,11 +312,6 @@ int capi_serialize(capi_handle_t h, int ss, int ds, const double* src, int64_t s
 // B(m x n, ldb) <- A(m x n, lda) on the handle's stream (the blocks may not overlap unless they coincide)
 __attribute__((visibility("hidden"))) int capi_internal_copy2d(capi_handle_t h, int64_t m, int64_t n, const double* A, int64_t lda, double* B, int64_t ldb) {
   if (m <= 0 || n <= 0 || (A == B && lda == ldb)) return CAPI_OK;
-  static const bool runtime_copy = getenv("CAPI_RUNTIME_COPY") != nullptr;      // A/B: the HIP runtime's blit kernels, as before round 4
-  if (runtime_copy) {
-    CAPI_HIP_CHECK(h, hipMemcpy2DAsync(B, sizeof(double) * ldb, A, sizeof(double) * lda, sizeof(double) * m, n, hipMemcpyDeviceToDevice, h->stream));
-    return CAPI_OK;
-  }
   if (lda == m && ldb == m && m * n >= (1 << 16) && (m > 8192 || n == 1)) {
     // contiguous on both sides: re-cut into columns of 8192 (eight 16-byte pieces in flight per thread), the rest as a short column behind them
     const int64_t total = m * n, cols = total / 8192, rest = total - cols * 8192;

@@ -124,8 +124,7 @@ protected:
     // CholeskyQR2 at the full-width kernels' shape (n = 256, tall, whole 32-row tiles): Q1 = A R1^-1 is never seen by the caller; it is
     // written by sweep 1 and read twice by sweep 2 as a panel32 image -- one contiguous stream per pass instead of 256 column streams
     // (CAPITAL_NO_PANEL32: column-major throughout, A/B).  The arithmetic, and so Q and R, are the same bit for bit.
-    const bool q1_tiled = args.num_iter > 1 && n == 256 && m_loc % 32 == 0 && m_loc >= 64 * n && !getenv("CAPITAL_NO_PANEL32") &&
-                          !getenv("CAPI_NO_TS") && !getenv("CAPI_TS_ROWS16");
+    const bool q1_tiled = args.num_iter > 1 && n == 256 && m_loc % 32 == 0 && m_loc >= 64 * n && !getenv("CAPITAL_NO_PANEL32");
     sweep_1d(A.data(), args.Q.data(), m_loc, n, args, CommInfo, false, q1_tiled);
     if (args.num_iter > 1) {
       args.R1._register_(n, n, 1, 1);

@@ -1,5 +1,5 @@
 """Tall-skinny Gram matrix and Q = A T at widths above 256 (CholeskyQR2 config 5: n = 1024): correctness against torch fp64
-on a ragged shape, then timings.   python tools/ts_wide_bench.py [log2_m ...] [--n 1024]   (A/B: CAPI_NO_TALL=1)"""
+on a ragged shape, then timings.   python tools/ts_wide_bench.py [log2_m ...] [--n 1024]"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
