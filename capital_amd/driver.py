@@ -62,6 +62,8 @@ def bind(D):
     D.capital_cacqr_get.argtypes = [_vp, _int, _dp]
     D.capital_cacqr_dims.argtypes = [_vp, C.POINTER(_i64), C.POINTER(_i64)]
     D.capital_cacqr_get_rows.argtypes = [_vp, _int, _i64, _i64, _dp]
+    D.capital_cacqr_set_shift.argtypes = [_vp, _int, _dbl]
+    D.capital_cacqr_sweep_stats.argtypes = [_vp, _int, _dp]
     return D
 
 
@@ -205,13 +207,19 @@ class Cholinv:
 
 class Cacqr:
     """qr::cacqr<SP,SaveIntermediates>::factor on this process's row-cyclic block of an m x n matrix
-    (bench/qr/cacqr.cpp:14-25: variant 1 = CholeskyQR, 2 = CholeskyQR2)."""
+    (bench/qr/cacqr.cpp:14-25: variant 1 = CholeskyQR, 2 = CholeskyQR2; up to 4 sweeps).  shifted: the first `shifted` of the `variant`
+    sweeps are shifted CholeskyQR sweeps (kappa(A) beyond 1e8: variant=3, shifted=1 up to ~1e10, variant=4, shifted=2 up to ~1e12; c = 1);
+    shift_scale multiplies the published shift."""
 
-    def __init__(self, m, n, c=1, variant=2, complete_inv=0, split=1, bc_mult=0, layout=0, num_chunks=0, serialize=True):
+    def __init__(self, m, n, c=1, variant=2, complete_inv=0, split=1, bc_mult=0, layout=0, num_chunks=0, serialize=True, shifted=0,
+                 shift_scale=1.0):
         self.D = load()
         self.p = self.D.capital_cacqr_create(m, n, c, variant, layout, num_chunks, int(complete_inv), split, bc_mult, int(serialize))
         if not self.p:
             raise DriverError("capital_cacqr_create: " + self.D.capital_drv_last_error().decode())
+        self.variant, self.shifted = variant, shifted
+        if shifted or shift_scale != 1.0:
+            _ck(self.D.capital_cacqr_set_shift(self.p, shifted, shift_scale), "set_shift")
         ml, nn = _i64(), _i64()
         _ck(self.D.capital_cacqr_dims(self.p, C.byref(ml), C.byref(nn)), "dims")
         self.m, self.n, self.m_loc = m, nn.value, ml.value
@@ -226,6 +234,18 @@ class Cacqr:
 
     def factor(self):
         _ck(self.D.capital_cacqr_factor(self.p), "factor")
+
+    def sweep_stats(self):
+        """Per sweep of the last factor() of a run with shifted sweeps: the shift s, the trace of the equilibrated Gram matrix (both 0
+        for a plain sweep) and cond_bound = ||R'||_1 ||R'||_inf ||R'^-1||_1 ||R'^-1||_inf of the sweep's Gram matrix G' = R'^T R'
+        (cond_2(G') <= cond_bound <= n^2 cond_2(G'); 1 for an orthonormal panel).  Watch the first plain sweep: below ~1e15 it is
+        safe, above ~1e16 n^2 a further shifted sweep is needed."""
+        out = []
+        for k in range(max(1, self.variant)):
+            v = (_dbl * 3)()
+            _ck(self.D.capital_cacqr_sweep_stats(self.p, k, v), "sweep_stats")
+            out.append({"shift": v[0], "trace": v[1], "cond_bound": v[2]})
+        return out
 
     def residual(self):
         v = _dbl()

@@ -100,6 +100,8 @@ struct cacqr_problem {
   virtual void get(int which, double* host) = 0;
   virtual void dims(int64_t* mloc, int64_t* n) = 0;
   virtual void get_rows(int which, int64_t row0, int64_t nrows, double* host) = 0;
+  virtual void set_shift(int num_shifted, double shift_scale) = 0;
+  virtual void sweep_stats(int k, double* out3) = 0;
 };
 
 template <class Alg>
@@ -114,6 +116,17 @@ struct cacqr_impl : cacqr_problem {
   void generate() override { A.distribute_random(grid.x, grid.y, grid.c, grid.d, grid.rank / grid.c); }             // bench/qr/cacqr.cpp:34
   void set_A(const double* host) override { A.from_host(host); }
   void factor() override { Alg::factor(A, pack, grid); }
+  void set_shift(int num_shifted, double shift_scale) override {
+    if (num_shifted < 0 || (size_t)num_shifted > std::max<size_t>(1, pack.num_iter) || !(shift_scale >= 0.0) || !(shift_scale <= 1.79e308))
+      throw std::invalid_argument("cacqr set_shift: 0 <= num_shifted <= the number of sweeps and a finite shift_scale >= 0 expected");
+    pack.num_shifted = (size_t)num_shifted;
+    pack.shift_scale = shift_scale;
+  }
+  // out3 = shift s, trace of the equilibrated Gram matrix, cond bound of sweep k of the last factor() (info::sweep_* in cacqr.h)
+  void sweep_stats(int k, double* out3) override {
+    if (k < 0 || (size_t)k >= pack.sweep_cond_bound.size()) throw std::invalid_argument("cacqr sweep_stats: no record of that sweep (records are kept by runs with shifted sweeps)");
+    out3[0] = pack.sweep_shift[k]; out3[1] = pack.sweep_trace[k]; out3[2] = pack.sweep_cond_bound[k];
+  }
   double residual() override { return qr::validate<Alg>::residual(A, pack, grid); }
   double orthogonality() override { return qr::validate<Alg>::orthogonality(A, pack, grid); }
   void get(int which, double* host) override {
@@ -212,6 +225,9 @@ void* capital_cacqr_create(int64_t m, int64_t n, int c, int variant, int layout,
 }
 int capital_cacqr_generate(void* p) { return guarded([&] { ((cacqr_problem*)p)->generate(); }); }
 int capital_cacqr_set_A(void* p, const double* host) { return guarded([&] { ((cacqr_problem*)p)->set_A(host); }); }
+// shifted CholeskyQR (cacqr.h): the first num_shifted of the `variant` sweeps are shifted sweeps; call before factor
+int capital_cacqr_set_shift(void* p, int num_shifted, double shift_scale) { return guarded([&] { ((cacqr_problem*)p)->set_shift(num_shifted, shift_scale); }); }
+int capital_cacqr_sweep_stats(void* p, int k, double* out3) { return guarded([&] { ((cacqr_problem*)p)->sweep_stats(k, out3); }); }
 int capital_cacqr_factor(void* p) { return guarded([&] { ((cacqr_problem*)p)->factor(); }); }
 int capital_cacqr_residual(void* p, double* out) { return guarded([&] { *out = ((cacqr_problem*)p)->residual(); }); }
 int capital_cacqr_orthogonality(void* p, double* out) { return guarded([&] { *out = ((cacqr_problem*)p)->orthogonality(); }); }

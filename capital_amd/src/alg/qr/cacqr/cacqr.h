@@ -9,6 +9,15 @@
 //     K8+K9  R = chol(G), R^-1 capi_dpotrf_trtri, replicated on every GPU
 //     K5  Q <- Q R^-1          capi_dtrmm_oop (right, upper), out of place into the block's second buffer
 // CholeskyQR2 runs the sweep twice and combines R = R2 R1 (cacqr.hpp:181-189, K6).
+// Beyond the reference (its sweep has no shift; CholeskyQR2 breaks down at kappa(A) ~ 1e8): info::num_iter is the total number of sweeps,
+// 1..4, R = R_k ... R_2 R_1, and the first info::num_shifted of them are SHIFTED sweeps (shifted CholeskyQR, Fukaya et al., SIAM J. Sci.
+// Comput. 42, 2020; 1-D variant only).  A shifted sweep differs from a plain one only around K8+K9: the reduced Gram matrix is column-
+// equilibrated by powers of two and shifted, G' = D^-1 G D^-1 + s I with s = shift_scale * 11 (m n + n (n + 1)) u trace(D^-1 G D^-1), m the
+// global row count (capi_dgram_equilibrate_shift), factored, and R = R' D, R^-1 = D^-1 R'^-1 (capi_dtri_rescale).  Its factorisation cannot
+// break down, and the panel it leaves has cond ~ sqrt(s) kappa(A): one shifted sweep serves kappa(A) up to ~1e10, two up to ~1e12.
+// The shifted sweeps precondition, the plain ones orthogonalise: num_iter - num_shifted >= 2 is what gives an orthogonal Q (with fewer
+// plain sweeps Q R = A still holds, Q^T Q = I does not).  s is computed after the all-reduce from identical bits in a fixed order, so
+// R stays bit-identical across the ranks.
 // Underneath, the A -> Q copy of factor() (cacqr.hpp:226) is folded into the first sweep (it reads A, writes Q) and the
 // second sweep ping-pongs between Q's data and scratch buffers, so every sweep streams the panel exactly twice
 // (read for the Gram, read+write for the solve) with no in-place hazard.
@@ -19,6 +28,11 @@
 #include "./../../matmult/summa/summa.h"
 #include "./../../cholesky/cholinv/cholinv.h"
 #include "./policy.h"
+
+// The two entry points of the shifted sweep are weak references: a stand-in of the C-ABI that does not have them (the CPU rehearsal
+// shim of the test suite) still links and loads, every other path runs on it, and invoke_1d refuses num_shifted > 0 there.
+#pragma weak capi_dgram_equilibrate_shift
+#pragma weak capi_dtri_rescale
 
 namespace qr {
 
@@ -37,8 +51,10 @@ public:
     using cholesky_inverse_type = CholeskyInversionType;
     template <typename CholeskyInversionArgType>
     info(size_t num_iter, CholeskyInversionArgType&& ci_args) : num_iter(num_iter), cholesky_inverse_args(std::forward<CholeskyInversionArgType>(ci_args)) {}
-    info(const info& p) : num_iter(p.num_iter), cholesky_inverse_args(p.cholesky_inverse_args) {}
-    const size_t num_iter;                                                       // 1: CholeskyQR, 2: CholeskyQR2 (bench/qr/cacqr.cpp:14,40)
+    info(const info& p) : num_iter(p.num_iter), num_shifted(p.num_shifted), shift_scale(p.shift_scale), cholesky_inverse_args(p.cholesky_inverse_args) {}
+    const size_t num_iter;                                                       // 1: CholeskyQR, 2: CholeskyQR2 (bench/qr/cacqr.cpp:14,40); up to 4 sweeps
+    size_t num_shifted = 0;                                                      // the first num_shifted sweeps are shifted (1-D variant); see the file comment
+    double shift_scale = 1.0;                                                    // multiplies the published shift 11 (m n + n (n + 1)) u ||A D^-1||_F^2
     typename CholeskyInversionType::template info<ScalarType, DimensionType> cholesky_inverse_args;
     matrix<ScalarType, DimensionType, rect> Q;
     matrix<ScalarType, DimensionType, typename SerializePolicy::structure> R;
@@ -48,6 +64,15 @@ public:
     // LAPACK info of the Gram matrix's factorisation (1-D variant): 0, or the first non-positive pivot (1-based) -- CholeskyQR's
     // known failure mode is a numerically rank-deficient A^T A (kappa(A) beyond ~1e8).  factor() throws std::domain_error then.
     int potrf_info = 0;
+    // per-sweep diagnostics of a run with num_shifted > 0, read back with potrf_info (one synchronisation, behind the launch chain):
+    // sweep_shift[k] = s and sweep_trace[k] = trace(D^-1 G D^-1) of a shifted sweep (0 for a plain one);
+    // sweep_cond_bound[k] = ||R'||_1 ||R'||_inf ||R'^-1||_1 ||R'^-1||_inf of the sweep's (equilibrated, shifted) Gram matrix G' = R'^T R':
+    // cond_2(G') <= sweep_cond_bound[k] <= n^2 cond_2(G'), and 1 for an orthonormal panel.  The Gram matrix of a SHIFTED sweep is capped near
+    // trace / s ~ 1 / (11 (m n + n^2) u) whatever kappa(A) is; the figure to watch is that of the first PLAIN sweep, a bound on the squared
+    // condition of the panel the shifted sweeps left: below ~1e15 that sweep is safe, above ~1e16 n^2 it cannot succeed and one more shifted
+    // sweep is needed; in between the bound does not decide (DESIGN.md section 2a has measured values).
+    std::vector<double> sweep_shift, sweep_trace, sweep_cond_bound;
+    matrix<ScalarType, DimensionType, rect> Dscale, SweepRec;                    // device: n column scales; 4 doubles per sweep
   };
 
   template <typename MatrixType, typename ArgType, typename CommType>
@@ -58,6 +83,9 @@ public:
     args.R._register_(gN, gN, CommInfo.c, CommInfo.c);
     if (CommInfo.c == 1) {
       invoke_1d(A, args, CommInfo);
+    } else if (args.num_shifted > 0) {
+      // the Gram block is element-cyclic on these grids: its diagonal and its trace live on different ranks
+      throw std::logic_error("qr::cacqr: shifted sweeps (num_shifted > 0) are built for the 1-D variant (c == 1) only");
     } else if (CommInfo.d % CommInfo.c == 0) {
       // c == d: one cube (sweep_3d); c < d: d/c cubes side by side (sweep_tune, cacqr.hpp:124-170) -- the same sweep per cube
       // plus one all-reduce of the Gram block across the cubes
@@ -65,7 +93,7 @@ public:
     } else {
       throw std::logic_error("qr::cacqr: the c x d x c grid needs c to divide d");
     }
-    if (!IP::keep_work) { args.G._destroy_(); args.Ginv._destroy_(); args.R1._destroy_(); args.Gpacked._destroy_(); }
+    if (!IP::keep_work) { args.G._destroy_(); args.Ginv._destroy_(); args.R1._destroy_(); args.Gpacked._destroy_(); args.Dscale._destroy_(); args.SweepRec._destroy_(); }
   }
 
   template <typename ArgType, typename CommType>
@@ -85,10 +113,11 @@ public:
 
 protected:
   // one CholeskyQR sweep: dst <- src * chol(src^T src)^-1 ; leaves R in args.G and R^-1 in args.Ginv
-  // src_tiled / dst_tiled: the panel is a "panel32" image (include/capital_hip.h) instead of column-major -- CholeskyQR2's intermediate Q1
+  // src_tiled / dst_tiled: the panel is a "panel32" image (include/capital_hip.h) instead of column-major -- the intermediate panels Q1, Q2, ..
+  // rec != nullptr (runs with num_shifted > 0): the sweep's 4-double device record; shifted: equilibrate and shift the Gram matrix (m_glob rows)
   template <typename ArgType, typename CommType>
   static void sweep_1d(const double* src, double* dst, int64_t m_loc, int64_t n, ArgType& args, CommType&& CommInfo, bool src_tiled = false,
-                       bool dst_tiled = false) {
+                       bool dst_tiled = false, bool shifted = false, double* rec = nullptr, int64_t m_glob = 0) {
     capi_handle_t h = capital::handle();
     CRITTER_START(CQR::gram);
     if (src_tiled) CAPITAL_CHECK(capi_dsyrk_panel32(h, n, m_loc, 1.0, src, 0.0, args.G.data(), n));                  // K7 on the image
@@ -104,7 +133,9 @@ protected:
     }
     CRITTER_STOP(CQR::gram);
     CRITTER_START(CQR::formR);
+    if (shifted) CAPITAL_CHECK(capi_dgram_equilibrate_shift(h, n, args.G.data(), n, m_glob, args.shift_scale, args.Dscale.data(), rec));
     CAPITAL_CHECK(capi_dpotrf_trtri(h, n, args.G.data(), n, args.Ginv.data(), n));                                    // K8 + K9
+    if (rec) CAPITAL_CHECK(capi_dtri_rescale(h, n, args.G.data(), n, args.Ginv.data(), n, shifted ? args.Dscale.data() : nullptr, rec));
     if (src_tiled || dst_tiled)
       CAPITAL_CHECK(capi_dtrmm_right_panel32(h, m_loc, n, 1.0, args.Ginv.data(), n, src, src_tiled ? 0 : m_loc, dst, dst_tiled ? 0 : m_loc));       // K5
     else
@@ -121,24 +152,48 @@ protected:
     if (SP::packed_gram) args.Gpacked._register_(n, n, 1, 1);
     CAPITAL_CHECK(capi_reset_info(h));
     args.potrf_info = 0;
-    // CholeskyQR2 at the full-width kernels' shape (n = 256, tall, whole 32-row tiles): Q1 = A R1^-1 is never seen by the caller; it is
-    // written by sweep 1 and read twice by sweep 2 as a panel32 image -- one contiguous stream per pass instead of 256 column streams
-    // (CAPITAL_NO_PANEL32: column-major throughout, A/B).  The arithmetic, and so Q and R, are the same bit for bit.
-    const bool q1_tiled = args.num_iter > 1 && n == 256 && m_loc % 32 == 0 && m_loc >= 64 * n && !getenv("CAPITAL_NO_PANEL32");
-    sweep_1d(A.data(), args.Q.data(), m_loc, n, args, CommInfo, false, q1_tiled);
-    if (args.num_iter > 1) {
+    const int64_t sweeps = std::max<int64_t>(1, (int64_t)args.num_iter), shifted = (int64_t)args.num_shifted;
+    if (sweeps > 4 || shifted > sweeps) throw std::invalid_argument("qr::cacqr: num_iter is 1..4 sweeps, of which num_shifted <= num_iter are shifted");
+    double* rec = nullptr;               // device records, 4 doubles per sweep (runs with shifted sweeps only)
+    if (shifted > 0) {
+      if (!&capi_dgram_equilibrate_shift || !&capi_dtri_rescale)
+        throw std::logic_error("qr::cacqr: this C-ABI library has no capi_dgram_equilibrate_shift / capi_dtri_rescale: no shifted sweeps");
+      args.Dscale._register_(1, n, 1, 1);
+      args.SweepRec._register_(4, 4, 1, 1);
+      rec = args.SweepRec.data();
+    }
+    // The full-width kernels' shape (n = 256, tall, whole 32-row tiles): the intermediate panels Q1 = A R1^-1, Q2, .. are never seen by the
+    // caller; each is written by one sweep and read twice by the next as a panel32 image -- one contiguous stream per pass instead of 256
+    // column streams (CAPITAL_NO_PANEL32: column-major throughout, A/B).  The arithmetic, and so Q and R, are the same bit for bit.
+    const bool q1_tiled = sweeps > 1 && n == 256 && m_loc % 32 == 0 && m_loc >= 64 * n && !getenv("CAPITAL_NO_PANEL32");
+    sweep_1d(A.data(), args.Q.data(), m_loc, n, args, CommInfo, false, q1_tiled, shifted > 0, rec, (int64_t)A.num_rows_global());
+    if (sweeps > 1) {
       args.R1._register_(n, n, 1, 1);
       capital::dev_copy(args.R1.data(), args.G.data(), n * n);                                                        // save_R_1d
-      sweep_1d(args.Q.data(), args.Q.scratch(), m_loc, n, args, CommInfo, q1_tiled, false);
-      args.Q.swap();
-      // R = R2 * R1 (cacqr.hpp:185-187): Ginv is free again and receives the product
-      CAPITAL_CHECK(capi_dtrmm_oop(h, CAPI_RIGHT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, n, n, 1.0, args.R1.data(), n, args.G.data(), n, args.Ginv.data(), n));
+      for (int64_t k = 1; k < sweeps; ++k) {
+        sweep_1d(args.Q.data(), args.Q.scratch(), m_loc, n, args, CommInfo, q1_tiled, q1_tiled && k + 1 < sweeps, k < shifted, rec ? rec + 4 * k : nullptr,
+                 (int64_t)A.num_rows_global());
+        args.Q.swap();
+        // R = R_k * (R_k-1 .. R1) (cacqr.hpp:185-187): Ginv is free again and receives the product
+        CAPITAL_CHECK(capi_dtrmm_oop(h, CAPI_RIGHT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, n, n, 1.0, args.R1.data(), n, args.G.data(), n, args.Ginv.data(), n));
+        if (k + 1 < sweeps) std::swap(args.R1.data(), args.Ginv.data());                                              // the product so far; the old one is overwritten next
+      }
       finalize_R(args.Ginv, args, n);
     } else {
       finalize_R(args.G, args, n);   // the reference leaves the Gram matrix in R here with Serialize; R is what is documented
     }
     // one 4-byte read behind the launch chain (the reference drops LAPACK's info, lapack/interface.hpp:39,54)
     CAPITAL_CHECK(capi_get_info(h, &args.potrf_info));
+    args.sweep_shift.clear(); args.sweep_trace.clear(); args.sweep_cond_bound.clear();
+    if (rec) {                                                                                                      // the stream is drained: a plain copy
+      double host[16];
+      CAPITAL_CHECK(capi_memcpy_d2h(h, host, rec, sizeof(double) * 4 * (size_t)sweeps));
+      for (int64_t k = 0; k < sweeps; ++k) {
+        args.sweep_shift.push_back(k < shifted ? host[4 * k] : 0.0);
+        args.sweep_trace.push_back(k < shifted ? host[4 * k + 1] : 0.0);
+        args.sweep_cond_bound.push_back(host[4 * k + 2] * host[4 * k + 3]);
+      }
+    }
     if (args.potrf_info != 0)
       throw std::domain_error("cacqr::factor: the Gram matrix is not positive definite (pivot " + std::to_string(args.potrf_info) +
                               "): A is numerically rank deficient for CholeskyQR; Q and R are not valid");

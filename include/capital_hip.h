@@ -116,6 +116,24 @@ int capi_dtrtri(capi_handle_t h, int uplo, int diag, int64_t n, double* A, int64
  * Rinv <- R^-1 (upper); strictly-lower parts of both outputs are zeroed (cyclic_to_local, util.hpp:131-164). */
 int capi_dpotrf_trtri(capi_handle_t h, int64_t n, double* A, int64_t lda, double* Rinv, int64_t ldi);
 int capi_get_info(capi_handle_t h, int* info);
+/* The n x n steps of a SHIFTED CholeskyQR sweep (qr::cacqr with num_shifted > 0).  They sit beside the reference's sweep,
+ * src/alg/qr/cacqr/cacqr.hpp:7-29, between its MPI_Allreduce of the Gram matrix and its cholinv call and behind that call.  Not in the
+ * reference: its sweep has no shift, and its CholeskyQR2 breaks down beyond kappa(A) ~ 1e8 (shifted CholeskyQR: Fukaya et al., SIAM J.
+ * Sci. Comput. 42, 2020).  rec[4] (DEVICE) is one sweep's record: s, trace(G'), ||R'||_1 ||R'||_inf, ||R'^-1||_1 ||R'^-1||_inf.
+ * capi_dgram_equilibrate_shift, in place on the upper triangle of G (the lower is neither read nor written):
+ *   e_j = floor(ex_j / 2), g_jj = f 2^ex_j with f in [0.5, 1) (the exponent is read from the bits, no log or sqrt), dscale[j] = 2^e_j;
+ *   G' = D^-1 G D^-1, D = diag(dscale): exact, and exactly equivariant under power-of-two column scalings of A;
+ *   rec[1] = trace(G') (>= ||A D^-1||_2^2), rec[0] = s = (shift_scale * (11 (m_global n + n (n + 1)) 2^-53)) * trace(G'); G' += s I.
+ *   A g_jj that is zero, negative or not finite sets the info word to j + 1 as a failed pivot does (its column stays unscaled).
+ *   The sums run in one workgroup in a fixed order: ranks that hold the same G compute the same s, bit for bit. */
+int capi_dgram_equilibrate_shift(capi_handle_t h, int64_t n, double* G, int64_t ldg, int64_t m_global, double shift_scale,
+                                 double* dscale, double* rec);
+/* Behind capi_dpotrf_trtri on G' + s I: R <- R' D (columns scaled), Rinv <- D^-1 R'^-1 (rows scaled), upper triangles, by adding the
+ * integer exponent (ldexp): exact.  rec[2] = ||R'||_1 ||R'||_inf >= ||R'||_2^2 and rec[3] = ||R'^-1||_1 ||R'^-1||_inf >= ||R'^-1||_2^2 of
+ * the UNSCALED factors: their product bounds cond_2(G' + s I) from above, is within n^2 of it, and is 1 for G' + s I = I.
+ * A diagonal entry r_jj or 1 / r_jj that leaves the normal range of fp64 when scaled (2^e_j too large or too small for it) sets the
+ * info word to j + 1, as a failed pivot.  dscale == NULL stands for D = I: R and Rinv are only read (the record of a plain sweep). */
+int capi_dtri_rescale(capi_handle_t h, int64_t n, double* R, int64_t ldr, double* Rinv, int64_t ldi, const double* dscale, double* rec);
 /* LAPACKE_dgeqrf / LAPACKE_dorgqr behind lapack::engine::_geqrf / _orgqr (lapack/interface.hpp:60-88; the reference has
  * the slots but no caller -- CholeskyQR2 is its QR).  Householder QR, LAPACK storage: R in the upper triangle, the
  * reflectors v_j (unit first entry implied) below it, tau[min(m,n)] on the DEVICE.  capi_dorgqr overwrites A (m x n,
