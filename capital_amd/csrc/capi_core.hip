@@ -23,7 +23,7 @@ extern "C" int capi_internal_copy2d(capi_handle_t h, int64_t m, int64_t n, const
 
 extern "C" {
 
-int capi_version(void) { return 100; }
+int capi_version(void) { return 101; }
 
 int capi_device_count(void) {
   int n = 0;

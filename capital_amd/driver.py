@@ -64,6 +64,7 @@ def bind(D):
     D.capital_cacqr_get_rows.argtypes = [_vp, _int, _i64, _i64, _dp]
     D.capital_cacqr_set_shift.argtypes = [_vp, _int, _dbl]
     D.capital_cacqr_sweep_stats.argtypes = [_vp, _int, _dp]
+    D.capital_cacqr_lstsq.argtypes = [_vp, _i64, _dp, _dp, _dp]
     return D
 
 
@@ -246,6 +247,20 @@ class Cacqr:
             _ck(self.D.capital_cacqr_sweep_stats(self.p, k, v), "sweep_stats")
             out.append({"shift": v[0], "trace": v[1], "cond_bound": v[2]})
         return out
+
+    def lstsq(self, B_local, residual=True):
+        """min ||A X - B||_F on the factors of the last factor() (qr::cacqr::least_squares, 1-D variant): X = R^-1 (Q^T B) on the device.
+        B_local: this rank's m_loc x r block of the right-hand sides, rows dealt as A's.  Returns (X, resnorms): X n x r, the same bits
+        on every rank; resnorms[j] = ||b_j - A x_j||_2 over all ranks, or None with residual=False."""
+        b = np.asfortranarray(B_local, dtype=np.float64)
+        if b.ndim == 1:
+            b = np.asfortranarray(b[:, None])
+        assert b.ndim == 2 and b.shape[0] == self.m_loc and b.shape[1] >= 1
+        r = b.shape[1]
+        X = np.zeros((self.n, r), order="F")
+        res = np.zeros(r) if residual else None
+        _ck(self.D.capital_cacqr_lstsq(self.p, r, b.ctypes.data_as(_dp), X.ctypes.data_as(_dp), res.ctypes.data_as(_dp) if residual else None), "lstsq")
+        return X, res
 
     def residual(self):
         v = _dbl()

@@ -102,6 +102,7 @@ struct cacqr_problem {
   virtual void get_rows(int which, int64_t row0, int64_t nrows, double* host) = 0;
   virtual void set_shift(int num_shifted, double shift_scale) = 0;
   virtual void sweep_stats(int k, double* out3) = 0;
+  virtual void lstsq(int64_t r, const double* B_host, double* X_host, double* resnorm_host) = 0;
 };
 
 template <class Alg>
@@ -126,6 +127,17 @@ struct cacqr_impl : cacqr_problem {
   void sweep_stats(int k, double* out3) override {
     if (k < 0 || (size_t)k >= pack.sweep_cond_bound.size()) throw std::invalid_argument("cacqr sweep_stats: no record of that sweep (records are kept by runs with shifted sweeps)");
     out3[0] = pack.sweep_shift[k]; out3[1] = pack.sweep_trace[k]; out3[2] = pack.sweep_cond_bound[k];
+  }
+  // min ||A X - B||_F on the factors of the last factor(): B_host is this rank's m_loc x r block (column-major, rows dealt as A's), X_host
+  // receives the n x r solution, resnorm_host (may be NULL: no residual pass) the r norms ||b_j - A x_j||_2
+  void lstsq(int64_t r, const double* B_host, double* X_host, double* resnorm_host) override {
+    if (r < 1 || !B_host || !X_host) throw std::invalid_argument("cacqr lstsq: r >= 1 right-hand sides, B and X expected");
+    MatrixType B(r, A.num_rows_global(), grid.c, grid.d);
+    B.from_host(B_host);
+    Alg::least_squares(A, B, pack, grid, resnorm_host != nullptr);
+    auto x = pack.X.to_host();
+    std::memcpy(X_host, x.data(), sizeof(double) * x.size());
+    if (resnorm_host) std::memcpy(resnorm_host, pack.ls_residual_norms.data(), sizeof(double) * (size_t)r);
   }
   double residual() override { return qr::validate<Alg>::residual(A, pack, grid); }
   double orthogonality() override { return qr::validate<Alg>::orthogonality(A, pack, grid); }
@@ -228,6 +240,10 @@ int capital_cacqr_set_A(void* p, const double* host) { return guarded([&] { ((ca
 // shifted CholeskyQR (cacqr.h): the first num_shifted of the `variant` sweeps are shifted sweeps; call before factor
 int capital_cacqr_set_shift(void* p, int num_shifted, double shift_scale) { return guarded([&] { ((cacqr_problem*)p)->set_shift(num_shifted, shift_scale); }); }
 int capital_cacqr_sweep_stats(void* p, int k, double* out3) { return guarded([&] { ((cacqr_problem*)p)->sweep_stats(k, out3); }); }
+// least squares on the factors (qr::cacqr::least_squares): after capital_cacqr_factor; resnorm_host_or_null == NULL skips the residual pass
+int capital_cacqr_lstsq(void* p, int64_t r, const double* B_host_local, double* X_host, double* resnorm_host_or_null) {
+  return guarded([&] { ((cacqr_problem*)p)->lstsq(r, B_host_local, X_host, resnorm_host_or_null); });
+}
 int capital_cacqr_factor(void* p) { return guarded([&] { ((cacqr_problem*)p)->factor(); }); }
 int capital_cacqr_residual(void* p, double* out) { return guarded([&] { *out = ((cacqr_problem*)p)->residual(); }); }
 int capital_cacqr_orthogonality(void* p, double* out) { return guarded([&] { *out = ((cacqr_problem*)p)->orthogonality(); }); }

@@ -18,6 +18,14 @@
 // The shifted sweeps precondition, the plain ones orthogonalise: num_iter - num_shifted >= 2 is what gives an orthogonal Q (with fewer
 // plain sweeps Q R = A still holds, Q^T Q = I does not).  s is computed after the all-reduce from identical bits in a fixed order, so
 // R stays bit-identical across the ranks.
+// Also beyond the reference (its cacqr.hpp stops at Q and R): least_squares(A, B, args, topo) after factor() solves min ||A X - B||_F for the
+// r columns of B as X = R^-1 (Q^T B) on the resident factors (1-D variant only), and returns the residual norms ||b_j - A x_j||_2:
+//     C = Q^T B              capi_dgemtn_ts on the local rows, <= CAPI_TS_MAX_RHS columns per call: a streaming kernel with an n x r output
+//                            (capi_dgemm(T, N) instead on tall panels of width >= 256: see least_squares)
+//     C = sum over ranks     capi_allreduce_sum over `world` (n r doubles), as the Gram matrix
+//     X = R^-1 C             capi_dtrsm on a full-storage image of R, replicated: identical bits in, identical bits out on every rank
+//     ||b_j - A x_j||^2      capi_dresid_ts on A (not Q), r doubles all-reduced, square roots on the host
+// No m x n temporary: the new device memory is B, X and the n x n image of R (the Gram work block, re-registered when the policy released it).
 // Underneath, the A -> Q copy of factor() (cacqr.hpp:226) is folded into the first sweep (it reads A, writes Q) and the
 // second sweep ping-pongs between Q's data and scratch buffers, so every sweep streams the panel exactly twice
 // (read for the Gram, read+write for the solve) with no in-place hazard.
@@ -33,6 +41,9 @@
 // shim of the test suite) still links and loads, every other path runs on it, and invoke_1d refuses num_shifted > 0 there.
 #pragma weak capi_dgram_equilibrate_shift
 #pragma weak capi_dtri_rescale
+// likewise the two streaming kernels of least_squares: without them factor() runs as before and least_squares refuses
+#pragma weak capi_dgemtn_ts
+#pragma weak capi_dresid_ts
 
 namespace qr {
 
@@ -73,12 +84,18 @@ public:
     // sweep is needed; in between the bound does not decide (DESIGN.md section 2a has measured values).
     std::vector<double> sweep_shift, sweep_trace, sweep_cond_bound;
     matrix<ScalarType, DimensionType, rect> Dscale, SweepRec;                    // device: n column scales; 4 doubles per sweep
+    // least_squares: the solution X (n x r, replicated on every rank), ||b_j - A x_j||_2 per right-hand side (empty when not asked for);
+    // factored: the last factor() came back with valid Q and R
+    matrix<ScalarType, DimensionType, rect> X, LsNorm2;
+    std::vector<double> ls_residual_norms;
+    bool factored = false;
   };
 
   template <typename MatrixType, typename ArgType, typename CommType>
   static void factor(const MatrixType& A, ArgType& args, CommType&& CommInfo) {
     static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "qr::cacqr requires matrices of rect structure");
     const auto gN = A.num_columns_global(), gM = A.num_rows_global();
+    args.factored = false;
     args.Q._register_(gN, gM, CommInfo.c, CommInfo.d);
     args.R._register_(gN, gN, CommInfo.c, CommInfo.c);
     if (CommInfo.c == 1) {
@@ -94,6 +111,55 @@ public:
       throw std::logic_error("qr::cacqr: the c x d x c grid needs c to divide d");
     }
     if (!IP::keep_work) { args.G._destroy_(); args.Ginv._destroy_(); args.R1._destroy_(); args.Gpacked._destroy_(); args.Dscale._destroy_(); args.SweepRec._destroy_(); }
+    args.factored = true;
+  }
+
+  // min ||A X - B||_F on the factors factor(A, args, CommInfo) left: args.X (n x r) and, with `residual`, args.ls_residual_norms.
+  // B is distributed exactly as A: matrix<double, int64_t, rect>(r, m, c, d), the same row-cyclic owner map.  See the file comment.
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void least_squares(const MatrixType& A, const MatrixType& B, ArgType& args, CommType&& CommInfo, bool residual = true) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "qr::cacqr requires matrices of rect structure");
+    if (CommInfo.c != 1) throw std::logic_error("qr::cacqr::least_squares is built for the 1-D variant (c == 1) only");
+    if (!&capi_dgemtn_ts || !&capi_dresid_ts)
+      throw std::logic_error("qr::cacqr: this C-ABI library has no capi_dgemtn_ts / capi_dresid_ts: no least-squares solve");
+    if (!args.factored || args.potrf_info != 0 || !args.Q.filled() || !args.R.filled())
+      throw std::logic_error("qr::cacqr::least_squares: factor() has not run or did not succeed: there is no valid Q and R to solve with");
+    capi_handle_t h = capital::handle();
+    const int64_t n = A.num_columns_global(), m_loc = A.num_rows_local(), r = B.num_columns_global();
+    if (r < 1 || B.num_rows_local() != m_loc || B.num_rows_global() != A.num_rows_global() || args.Q.num_rows_local() != m_loc ||
+        args.Q.num_columns_global() != n)
+      throw std::invalid_argument("qr::cacqr::least_squares: B must have r >= 1 columns and A's rows, distributed as A, and A must be the factored matrix");
+    CRITTER_START(CQR::lstsq);
+    if (args.X.filled() && args.X.num_columns_local() != r) args.X._destroy_();
+    args.X._register_(r, n, 1, 1);
+    const int64_t W = CAPI_TS_MAX_RHS;
+    // C = Q^T B (the last sweep leaves Q column-major).  capi_dgemtn_ts as it stands is UNMEASURED.  An earlier form of it lost to
+    // capi_dgemm(T, N) on the 128-tile kernel on both shapes that were timed, 2^22 x 256 (3.7-3.9 against 2.5-2.8 ms) and 2^21 x 1024
+    // (DESIGN.md section 4); on that evidence tall panels of width >= 256 take that product.  Narrower or shorter panels take the
+    // streaming kernel; no form of it was timed there.
+    const bool by_gemm = n >= 256 && m_loc >= 64 * n;
+    for (int64_t j = 0; j < r; j += W) {
+      const int64_t rb = std::min(W, r - j);
+      if (by_gemm) CAPITAL_CHECK(capi_dgemm(h, CAPI_TRANS, CAPI_NOTRANS, n, rb, m_loc, 1.0, args.Q.data(), m_loc, B.data() + j * m_loc, m_loc, 0.0, args.X.data() + j * n, n));
+      else CAPITAL_CHECK(capi_dgemtn_ts(h, m_loc, n, rb, 1.0, args.Q.data(), m_loc, B.data() + j * m_loc, m_loc, 0.0, args.X.data() + j * n, n));
+    }
+    if (CommInfo.size > 1) CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, args.X.data(), n * r));
+    args.G._register_(n, n, 1, 1);                                                                                  // full-storage image of R
+    serialize<uppertri, uppertri>::invoke(args.R, args.G, 0, n, 0, n, 0, n, 0, n);
+    CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, n, r, 1.0, args.G.data(), n, args.X.data(), n));   // X = R^-1 C
+    args.ls_residual_norms.clear();
+    if (residual) {
+      if (args.LsNorm2.filled() && args.LsNorm2.num_columns_local() != r) args.LsNorm2._destroy_();
+      args.LsNorm2._register_(r, 1, 1, 1);
+      for (int64_t j = 0; j < r; j += W)
+        CAPITAL_CHECK(capi_dresid_ts(h, m_loc, n, std::min(W, r - j), A.data(), m_loc, args.X.data() + j * n, n, B.data() + j * m_loc, m_loc, nullptr, 0,
+                                     args.LsNorm2.data() + j));
+      if (CommInfo.size > 1) CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, args.LsNorm2.data(), r));
+      args.ls_residual_norms = args.LsNorm2.to_host();
+      for (double& v : args.ls_residual_norms) v = std::sqrt(v);
+    }
+    if (!IP::keep_work) { capital::sync(); args.G._destroy_(); }
+    CRITTER_STOP(CQR::lstsq);
   }
 
   template <typename ArgType, typename CommType>

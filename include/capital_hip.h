@@ -134,6 +134,19 @@ int capi_dgram_equilibrate_shift(capi_handle_t h, int64_t n, double* G, int64_t 
  * A diagonal entry r_jj or 1 / r_jj that leaves the normal range of fp64 when scaled (2^e_j too large or too small for it) sets the
  * info word to j + 1, as a failed pivot.  dscale == NULL stands for D = I: R and Rinv are only read (the record of a plain sweep). */
 int capi_dtri_rescale(capi_handle_t h, int64_t n, double* R, int64_t ldr, double* Rinv, int64_t ldi, const double* dscale, double* rec);
+/* Streaming tall-skinny products with a NARROW output, for least-squares solves on the CholeskyQR factors (qr::cacqr::least_squares: X = R^-1
+ * (Q^T B) and the residual B - A X).  Not in the reference: src/alg/qr/cacqr/cacqr.hpp stops at Q and R.  1 <= r <= CAPI_TS_MAX_RHS right-hand
+ * sides per call (more: CAPI_EINVAL, nothing is touched; the caller loops over column blocks); tall m >= 0, n >= 1, any leading dimensions >= the
+ * row counts, pointers aligned to 8 bytes (16 bytes and even leading dimensions take the faster loads).  A is read from HBM once per call, no
+ * n-wide or m-long temporary; partial sums over row slices are combined in a fixed order: bit-identical from run to run, no atomics.
+ * capi_dgemtn_ts: C (n x r) <- alpha A^T B + beta C, A m x n, B m x r (beta == 0: C is not read; m == 0: C <- beta C). */
+enum { CAPI_TS_MAX_RHS = 32 };
+int capi_dgemtn_ts(capi_handle_t h, int64_t m, int64_t n, int64_t r, double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
+                   double beta, double* C, int64_t ldc);
+/* capi_dresid_ts: Rout (m x r) <- B - A X, X n x r, and colnorm2[j] <- sum_i Rout(i, j)^2 (DEVICE, r doubles).  Rout == NULL: the norms alone;
+ * Rout == B: in place; colnorm2 == NULL: the residual alone; m == 0: colnorm2 <- 0. */
+int capi_dresid_ts(capi_handle_t h, int64_t m, int64_t n, int64_t r, const double* A, int64_t lda, const double* X, int64_t ldx,
+                   const double* B, int64_t ldb, double* Rout, int64_t ldr, double* colnorm2);
 /* LAPACKE_dgeqrf / LAPACKE_dorgqr behind lapack::engine::_geqrf / _orgqr (lapack/interface.hpp:60-88; the reference has
  * the slots but no caller -- CholeskyQR2 is its QR).  Householder QR, LAPACK storage: R in the upper triangle, the
  * reflectors v_j (unit first entry implied) below it, tau[min(m,n)] on the DEVICE.  capi_dorgqr overwrites A (m x n,
