@@ -444,23 +444,20 @@ private:
         // partner-exchanged copy of R11^-1 (cholinv.hpp:116-117)
         view Tx{ws.take((int64_t)split1 * split1), split1, split1, split1};
         // (on a grid that relays every rank joins the exchange with the same, packed, count: the diagonal ranks carry other pairs' units)
-        if ((t.x == t.y && !t.multipath) || getenv("CAPITAL_NO_PACKED_COMM")) {
+        const int64_t np = matmult::summa::tri_count(split1);
+        if ((t.x == t.y && !t.multipath) || !matmult::summa::packed_comm()) {
           CAPITAL_CHECK(capi_dlacpy(h, 0, split1, split1, R11i.p, ld, Tx.p, Tx.ld));
           util::transpose_raw(Tx.p, Tx.count(), ws.take(Tx.count()), t, matmult::summa::relay_space(t, Tx.count(), ws));
         } else if (t.x == t.y) {
-          const int64_t np = (int64_t)split1 * (split1 + 1) / 2;
           CAPITAL_CHECK(capi_dlacpy(h, 0, split1, split1, R11i.p, ld, Tx.p, Tx.ld));
           util::transpose_raw(nullptr, np, nullptr, t, matmult::summa::relay_space(t, np, ws));
         } else {
           // the exchanged block is upper triangular: it crosses the link packed (n(n+1)/2) and is unpacked on arrival;
           // the strictly-lower half of Tx is never read (TRMM masks by selection)
-          const int64_t np = (int64_t)split1 * (split1 + 1) / 2;
           double* pk = ws.take(np);
-          CAPITAL_CHECK(capi_serialize_shape(h, CAPI_UPPERTRI, CAPI_RECT, CAPI_UPPERTRI, R11i.p, split1, ld, pk, split1, split1,
-                                             0, split1, 0, split1, 0, split1, 0, split1));
+          matmult::summa::pack_tri(R11i, CAPI_UPPER, pk);
           util::transpose_raw(pk, np, ws.take(np), t, matmult::summa::relay_space(t, np, ws));
-          CAPITAL_CHECK(capi_serialize_shape(h, CAPI_UPPERTRI, CAPI_UPPERTRI, CAPI_RECT, pk, split1, split1, Tx.p, split1, split1,
-                                             0, split1, 0, split1, 0, split1, 0, split1));
+          matmult::summa::unpack_tri(pk, CAPI_UPPER, Tx);
         }
         matmult::summa::trmm(t, CAPI_LEFT, CAPI_UPPER, CAPI_TRANS, CAPI_NONUNIT, 1.0, Tx, A12, W, ws);
       }

@@ -14,6 +14,9 @@
 //     (summa.hpp:115-146 runs cblas_dgemm and repacks);
 //   * any c dividing d is accepted: layer z owns K-classes q = z, z+c, ... (the reference needs c == d);
 //     d == 1 with c > 1 slices the local K range instead (pure replication, used for the 2-GPU grid).
+// With num_chunks > 0 the collectives of a multiply overlap its tile kernels, column chunk by column chunk.  That pipeline is built
+// once (struct chunks, struct pipe, stream_chunks, depth_sum: see the table in front of them); gemm, trmm and syrk supply their whole
+// operand and their local products per chunk.  The unpiped branches and colsplit_run keep schedules of their own.
 #ifndef CAPITAL_MATMULT_SUMMA_H_
 #define CAPITAL_MATMULT_SUMMA_H_
 
@@ -102,8 +105,7 @@ public:
 
   // ---- view-level engine (used directly by cholinv / cacqr) ---------------------------------------------------------
   // C <- alpha*op(A)*op(B) + beta*C.  Operand blocks are the LOCAL blocks of this rank; roots are chosen per K-class.
-  // With num_chunks > 0 (one K-class per layer, op(B) = B): A first, then B and the product column chunk by column chunk --
-  // bcast of chunk j+1 || MFMA on chunk j || depth all-reduce of chunk j-1 (summa.hpp:195-215,238-249).
+  // With num_chunks > 0 (op(B) = B) the chunk pipeline below: A whole, B and the product column chunk by column chunk.
   template <typename CommType>
   static void gemm(CommType&& t, int transA, int transB, double alpha, view A, view B, double beta, view C, arena& ws) {
     capi_handle_t h = capital::handle();
@@ -125,9 +127,8 @@ public:
     view acc = t.c > 1 ? view{ws.take(M * N), M, M, N} : C;
     const size_t steps = t.d > 1 ? t.d / t.c : 1;
     const bool piped = t.num_chunks > 0 && transB == CAPI_NOTRANS && (t.d > 1 || t.c > 1);
-    const int nch = piped ? chunk_count(t.num_chunks, N) : 1;
-    pipe P(piped && nch > 1);
-    enum { E0 = 0, EA = 1, EB = 2, EC = 70, ER = 140 };
+    const chunks plan{N, piped ? chunk_count(t.num_chunks, N) : 1};
+    pipe P(piped && plan.nch > 1);
     if (!P.on) {
       if (t.d == 1) {
         // pure replication: layer z multiplies its slice of the local K range
@@ -144,103 +145,152 @@ public:
         }
       }
       if (t.c > 1) {
-        allreduce_depth(t, acc.p, acc.count(), ws);
+        allreduce_view(t, acc, ws);
         CAPITAL_CHECK(capi_dgeadd(h, 0, M, N, 1.0, acc.p, acc.ld, beta, C.p, C.ld));
       }
       ws.top = mark;
       return;
     }
     // ---- pipelined over the output's column chunks; every K-class step s of this layer contributes to every chunk
+    //      (d == 1: nothing travels before the depth sum, layer z multiplies its slice [k0,k1) of the local K range)
     const bool sliced = (t.d == 1);
     int64_t k0 = 0, k1 = K;
-    std::vector<view> a(steps, A), b(steps, B);
-    P.main(); P.rec(E0);
-    P.comm(); P.wait(E0);
-    if (sliced) {
-      kslice(K, t.c, t.z, k0, k1);
-    } else {
-      for (size_t s = 0; s < steps; ++s) {
-        a[s] = panel(t, AX_ROW, s, A, ws);
-        const bool rootB = t.y == t.z + s * t.c;
-        b[s] = view{(rootB && B.contiguous()) ? B.p : ws.take(B.count()), B.rows, B.rows, B.cols};
-      }
-    }
-    P.rec(EA);
-    int64_t cmax = 0;
-    for (int j = 0; j < nch; ++j) { int64_t c0, c1; chunk_range(N, nch, j, c0, c1); cmax = std::max(cmax, c1 - c0); }
-    double* relay = relay_space(t, std::max(B.rows, acc.rows) * cmax, ws);
-    for (int j = 0; j < nch; ++j) {
-      int64_t c0, c1;
-      chunk_range(N, nch, j, c0, c1);
-      if (!sliced && c1 > c0)
-        for (size_t s = 0; s < steps; ++s) {
-          const bool rootB = t.y == t.z + s * t.c;
-          if (rootB && !B.contiguous()) CAPITAL_CHECK(capi_dlacpy(h, 0, B.rows, c1 - c0, B.p + c0 * B.ld, B.ld, b[s].p + c0 * b[s].ld, b[s].ld));
-          bcast_axis(t, AX_COLUMN, s, b[s].p + c0 * b[s].ld, b[s].rows * (c1 - c0), relay);
-        }
-      P.rec(EB + j);
-    }
-    P.main(); P.wait(EA);
-    for (int j = 0; j < nch; ++j) {
-      int64_t c0, c1;
-      chunk_range(N, nch, j, c0, c1);
+    if (sliced) kslice(K, t.c, t.z, k0, k1);
+    std::vector<view> a(steps, A);
+    P.begin();
+    if (!sliced)
+      for (size_t s = 0; s < steps; ++s) a[s] = panel(t, AX_ROW, s, A, ws);
+    P.whole_sent();
+    double* relay = relay_space(t, std::max(B.rows, acc.rows) * plan.widest(), ws);      // (one buffer for stages 3 and 5)
+    const std::vector<view> b = stream_chunks(t, P, AX_COLUMN, sliced ? 0 : steps, B, plan, relay, ws);
+    P.resume();
+    P.products(plan, [&](int j, int64_t c0, int64_t c1) {
       P.wait(EB + j);
-      if (c1 > c0)
-        for (size_t s = 0; s < steps; ++s) {
-          const double bt = s ? 1.0 : (t.c > 1 ? 0.0 : beta);
-          const double* ap = sliced ? (transA ? a[s].p + k0 : a[s].p + k0 * a[s].ld) : a[s].p;
-          CAPITAL_CHECK(capi_dgemm(h, transA, CAPI_NOTRANS, M, c1 - c0, k1 - k0, alpha, ap, a[s].ld, b[s].p + k0 + c0 * b[s].ld, b[s].ld, bt,
-                                   acc.p + c0 * acc.ld, acc.ld));
-        }
-      P.rec(EC + j);
-    }
-    if (t.c > 1) {
-      P.comm();
-      double* half = depth_space(t, acc.rows * cmax, ws);
-      for (int j = 0; j < nch; ++j) {
-        int64_t c0, c1;
-        chunk_range(N, nch, j, c0, c1);
-        P.wait(EC + j);
-        if (c1 > c0) allreduce_depth(t, acc.p + c0 * acc.ld, acc.rows * (c1 - c0), half, relay);
+      for (size_t s = 0; c1 > c0 && s < steps; ++s) {
+        const double bt = s ? 1.0 : (t.c > 1 ? 0.0 : beta);
+        const double* ap = sliced ? (transA ? a[s].p + k0 : a[s].p + k0 * a[s].ld) : a[s].p;
+        CAPITAL_CHECK(capi_dgemm(h, transA, CAPI_NOTRANS, M, c1 - c0, k1 - k0, alpha, ap, a[s].ld, b[s].p + k0 + c0 * b[s].ld, b[s].ld, bt,
+                                 acc.p + c0 * acc.ld, acc.ld));
       }
-      P.rec(ER);
-      P.main(); P.wait(ER);
-      CAPITAL_CHECK(capi_dgeadd(h, 0, M, N, 1.0, acc.p, acc.ld, beta, C.p, C.ld));
-    } else {
-      P.main();
-    }
+    });
+    depth_sum(t, P, plan, acc, [&](int64_t) { return acc.rows; }, relay, ws);
+    if (t.c > 1) CAPITAL_CHECK(capi_dgeadd(h, 0, M, N, 1.0, acc.p, acc.ld, beta, C.p, C.ld));
     ws.top = mark;
   }
 
-  // Cross-stream pipeline helper: with num_chunks > 0 the collectives of a multiply run on the handle's communication
-  // stream beside the tile kernel on the compute stream (the reference's MPI_Ibcast/MPI_Iallreduce chunking,
-  // summa.hpp:195-215,238-249).  Host calls are issued in an order that is also valid when executed sequentially.
+  // ---- the column-chunk pipeline (num_chunks > 0; the reference's MPI_Ibcast/MPI_Iallreduce chunking, summa.hpp:195-215,238-249) ----
+  // The collectives of a multiply run on the handle's communication stream beside the tile kernel on the compute stream:
+  // bcast of chunk j+1 || MFMA on chunk j || depth all-reduce of chunk j-1.  gemm, trmm and syrk share every stage but the fourth:
+  //   1  pipe::begin      the communication stream joins the compute stream (E0)
+  //   2  (the multiply), pipe::whole_sent   its "whole" operand travels first: the A panels / the packed T panels / the exchanged L
+  //                       panels of every step, then EW
+  //   3  stream_chunks    the other operand travels by column chunks, every K-class step of a chunk, then EB + j
+  //   4  pipe::resume, pipe::products   compute stream: behind EW, per chunk the multiply's callable -- its wait for EB + j and its local
+  //                       products summed over the steps --, then EC + j
+  //   5  depth_sum        c > 1: communication stream, per chunk behind EC + j a depth all-reduce of the chunk, then ER, which the compute
+  //                       stream awaits
+  // Host calls are issued in an order that is also valid when executed sequentially.
+
+  // how N columns are cut into nch chunks (multiples of 2 columns keep 16-byte alignment; trailing chunks can be empty)
+  struct chunks {
+    int64_t N;
+    int nch;
+    struct span {
+      int64_t c0, c1;
+      bool empty() const { return c1 <= c0; }
+      int64_t width() const { return c1 - c0; }
+    };
+    span range(int j) const {
+      const int64_t per = ((N + nch - 1) / nch + 1) & ~(int64_t)1;
+      const int64_t c0 = std::min<int64_t>(N, per * j);
+      return span{c0, std::min<int64_t>(N, c0 + per)};
+    }
+    int64_t widest() const { return range(0).width(); }          // (every chunk in front of the last non-empty one has the full width)
+    template <typename F>
+    void each(F&& f) const {                                     // f(j, c0, c1) for the non-empty chunks
+      for (int j = 0; j < nch; ++j) {
+        const span r = range(j);
+        if (!r.empty()) f(j, r.c0, r.c1);
+      }
+    }
+  };
   struct pipe {
+    // event slots of one multiply, counted from its rolling base: EW = the whole operand, EB + j / EC + j = chunk j has arrived / is
+    // computed, ER = the depth sum.  (cholinv.h's own events sit at 1000 and above.)
+    enum { E0 = 0, EW = 1, EB = 2, EC = 70, ER = 140, MAX_CHUNKS = 64, SLOTS = 256, BASES = 4 };
+    static_assert(EB + MAX_CHUNKS <= EC && EC + MAX_CHUNKS <= ER && ER < SLOTS && SLOTS * (BASES - 1) + ER < 1000,
+                  "at most MAX_CHUNKS chunks fit between the slots, and every base + slot stays below cholinv.h's events");
     capi_handle_t h;
     bool on;
     int base;
     explicit pipe(bool enable) : h(capital::handle()), on(enable) {
       static CAPITAL_RANK_LOCAL int next = 0;
       base = next;
-      next = (next + 256) % 1024;
+      next = (next + SLOTS) % (SLOTS * BASES);
     }
     void comm() { if (on) CAPITAL_CHECK(capi_stream_select(h, 1)); }
     void main() { if (on) CAPITAL_CHECK(capi_stream_select(h, 0)); }
     void rec(int s) { if (on) CAPITAL_CHECK(capi_event_record(h, base + s)); }
     void wait(int s) { if (on) CAPITAL_CHECK(capi_event_wait(h, base + s)); }
+    // stage 1: what follows runs on the communication stream, behind everything enqueued so far
+    void begin() { main(); rec(E0); comm(); wait(E0); }
+    // stage 2 is complete: the whole operand has been enqueued
+    void whole_sent() { rec(EW); }
+    // stage 4: back on the compute stream, behind the whole operand ...
+    void resume() { main(); wait(EW); }
+    // ... and per chunk: local(j, c0, c1) waits for the chunk's arrival -- its first statement is the wait for EB + j, the consumer side of
+    // stream_chunks' record, kept beside the products that read the chunk (the negative test of tests/test_gpu_multirank.py builds the
+    // host layer without exactly these lines) -- and enqueues the chunk's products unless the chunk is empty; its completion is recorded here
+    template <typename Local>
+    void products(const chunks& plan, Local&& local) {
+      for (int j = 0; j < plan.nch; ++j) {
+        const chunks::span r = plan.range(j);
+        local(j, r.c0, r.c1);
+        rec(EC + j);
+      }
+    }
   };
+  static constexpr int EB = pipe::EB;                            // (the name under which the multiplies wait for chunk j)
   static int chunk_count(size_t num_chunks, int64_t cols) {
     // (a chunk costs two cross-stream hand-offs -- event record on one HIP stream, wait on the other: tens of microseconds between two
     //  hardware queues, measured in round 3 --, so it has to carry work in the 100-microsecond range: 512 columns; tests shrink it)
     static const int64_t min_cols = getenv("CAPITAL_MIN_CHUNK_COLS") ? std::max(2, atoi(getenv("CAPITAL_MIN_CHUNK_COLS"))) : 512;
-    int n = (int)std::min<int64_t>((int64_t)std::min<size_t>(num_chunks, 64), std::max<int64_t>(cols / min_cols, 1));
+    int n = (int)std::min<int64_t>((int64_t)std::min<size_t>(num_chunks, pipe::MAX_CHUNKS), std::max<int64_t>(cols / min_cols, 1));
     return n < 1 ? 1 : n;
   }
-  // column range of chunk j (multiples of 2 columns keep 16-byte alignment)
-  static void chunk_range(int64_t cols, int nch, int j, int64_t& c0, int64_t& c1) {
-    const int64_t per = ((cols + nch - 1) / nch + 1) & ~(int64_t)1;
-    c0 = std::min<int64_t>(cols, per * j);
-    c1 = std::min<int64_t>(cols, c0 + per);
+  // stage 3, on the communication stream: `src` travels along `axis` column chunk by column chunk, for every one of the layer's `steps`
+  // K-class steps.  Returns where step s of it lands (the root's own block if that is contiguous).  steps == 0: every layer holds src
+  // already (d == 1), only the events are recorded.  The landing views and `relay` (sized for src.rows * plan.widest()) must stay
+  // allocated until the multiply's last event.
+  template <typename CommType>
+  static std::vector<view> stream_chunks(CommType&& t, pipe& P, int axis, size_t steps, const view& src, const chunks& plan, double* relay, arena& ws) {
+    std::vector<view> land(std::max<size_t>(steps, 1), src);
+    for (size_t s = 0; s < steps; ++s) land[s] = landing(is_root(t, axis, s), src, ws);
+    for (int j = 0; j < plan.nch; ++j) {
+      const chunks::span r = plan.range(j);
+      if (!r.empty())
+        for (size_t s = 0; s < steps; ++s) {
+          stage(is_root(t, axis, s), src, land[s], r.c0, r.c1);
+          bcast_axis(t, axis, s, land[s].p + r.c0 * land[s].ld, land[s].rows * r.width(), relay);
+        }
+      P.rec(pipe::EB + j);
+    }
+    return land;
+  }
+  // stage 5: the sum over depth of the accumulator's column chunks, each behind its products; of chunk [c0,c1) the leading rows_of(c1)
+  // rows travel (all of them, or c1 for an upper-triangular output).  `relay` sized for acc.rows * plan.widest().  Ends on the compute stream.
+  template <typename CommType, typename RowsOf>
+  static void depth_sum(CommType&& t, pipe& P, const chunks& plan, const view& acc, RowsOf&& rows_of, double* relay, arena& ws) {
+    if (t.c == 1) { P.main(); return; }
+    P.comm();
+    double* half = depth_space(t, acc.rows * plan.widest(), ws);
+    for (int j = 0; j < plan.nch; ++j) {
+      const chunks::span r = plan.range(j);
+      P.wait(pipe::EC + j);
+      if (!r.empty()) allreduce_view(t, view{acc.p + r.c0 * acc.ld, acc.ld, rows_of(r.c1), r.width()}, half, relay, ws);
+    }
+    P.rec(pipe::ER);
+    P.main(); P.wait(pipe::ER);
   }
 
   // Cout <- alpha*op(T)*B (Left) or alpha*B*op(T) (Right); T is this rank's block of a triangular matrix.
@@ -275,27 +325,24 @@ public:
     }
     const int64_t mark = ws.top;
     const size_t steps = t.d > 1 ? t.d / t.c : 1;
-    // The output-column pipeline serves the one-step cases (c == d as in the reference, or d == 1): every left multiply, and the
-    // right multiply with an upper, untransposed T (the inverse completion, cholinv.hpp:150-154; cacqr.hpp:108-112) -- there column
-    // chunk j of the output needs B's column chunks 0..j, which arrive in that order.
+    // The output-column pipeline serves every left multiply, and the right multiply with an upper, untransposed T (the inverse
+    // completion, cholinv.hpp:150-154; cacqr.hpp:108-112) -- there column chunk j of the output needs B's column chunks 0..j, which
+    // arrive in that order.
     const bool piped_left = side == CAPI_LEFT;
     const bool piped_right = side == CAPI_RIGHT && eff_upper && trans == CAPI_NOTRANS && t.d > 1;
     const bool piped = t.num_chunks > 0 && (piped_left || piped_right) && Cout.contiguous();
-    const int nch = piped ? chunk_count(t.num_chunks, N) : 1;
-    pipe P(piped && nch > 1);
-    enum { E0 = 0, ET = 1, EB = 2, EC = 70, ER = 140 };
-    int64_t cmax = N;
-    if (P.on) { cmax = 0; for (int j = 0; j < nch; ++j) { int64_t c0, c1; chunk_range(N, nch, j, c0, c1); cmax = std::max(cmax, c1 - c0); } }
+    const chunks plan{N, piped ? chunk_count(t.num_chunks, N) : 1};
+    pipe P(piped && plan.nch > 1);
+    double* relay = nullptr;                                     // (B and Cout are M x N: one buffer for stages 3 and 5)
     if (t.d == 1) {
-      // K-slice [k0,k1) of a triangular operand: a triangle on the diagonal plus a rectangle beside it
+      // K-slice [k0,k1) of a triangular operand: a triangle on the diagonal plus a rectangle beside it.  Nothing travels before the
+      // depth sum, so of the pipeline only stage 5 runs (left multiply), behind the EC + j recorded here.
       const int64_t K = T.rows;
       int64_t k0, k1;
       kslice(K, t.c, t.z, k0, k1);
-      for (int j = 0; j < nch; ++j) {
-        int64_t c0 = 0, c1 = N;
-        if (nch > 1) chunk_range(N, nch, j, c0, c1);
+      if (P.on) relay = relay_space(t, M * plan.widest(), ws);
+      plan.each([&](int j, int64_t c0, int64_t c1) {
         const int64_t nc = c1 - c0;
-        if (nc <= 0) continue;
         if (side == CAPI_LEFT) {
           const double* Bj = B.p + c0 * B.ld;
           double* Cj = Cout.p + c0 * Cout.ld;
@@ -311,8 +358,8 @@ public:
               CAPITAL_CHECK(capi_dgemm(h, trans, CAPI_NOTRANS, r1 - r0, nc, k1 - k0, alpha, Tr, T.ld, Bj + k0, B.ld, 0.0, Cj + r0, Cout.ld));
             }
           }
-          P.rec(EC + j);
-        } else {
+          P.rec(pipe::EC + j);                   // (by hand: pipe::products would wait for an EB + j that nobody records here)
+        } else {                                                                         // (never chunked: one pass over all of N)
           CAPITAL_CHECK(capi_dgeadd(h, 0, M, N, 0.0, Cout.p, Cout.ld, 0.0, Cout.p, Cout.ld));
           if (k1 > k0) {
             const double* Tkk = T.p + k0 + k0 * T.ld;
@@ -325,7 +372,7 @@ public:
             }
           }
         }
-      }
+      });
     } else if (!P.on) {
       for (size_t s = 0; s < steps; ++s) {
         view tt, bb;
@@ -334,72 +381,34 @@ public:
         CAPITAL_CHECK(capi_dtrmm_acc(h, side, uplo, trans, diag, M, N, alpha, tt.p, tt.ld, bb.p, bb.ld, s ? 1.0 : 0.0, Cout.p, Cout.ld));
       }
     } else {
-      // every K-class step of this layer: the T panels first (whole, packed), then the B panels column chunk by column chunk on the
-      // communication stream; chunk j of the output sums the steps' products
+      // the T panels of every K-class step first (whole, packed), then the B panels column chunk by column chunk
       const int axT = side == CAPI_LEFT ? AX_ROW : AX_COLUMN, axB = side == CAPI_LEFT ? AX_COLUMN : AX_ROW;
-      P.main(); P.rec(E0);
-      P.comm(); P.wait(E0);
-      std::vector<view> tt(steps, T), bb(steps, view{nullptr, B.rows, B.rows, B.cols});
+      std::vector<view> tt(steps, T);
+      P.begin();
       for (size_t s = 0; s < steps; ++s) tt[s] = panel_tri(t, axT, s, T, uplo, ws);
-      P.rec(ET);
-      for (size_t s = 0; s < steps; ++s) {
-        const bool rootB = (side == CAPI_LEFT ? t.y : t.x) == t.z + s * t.c;
-        bb[s].p = (rootB && B.contiguous()) ? B.p : ws.take(B.count());
-      }
-      double* relay = relay_space(t, B.rows * cmax, ws);
-      for (int j = 0; j < nch; ++j) {
-        int64_t c0, c1;
-        chunk_range(N, nch, j, c0, c1);
-        if (c1 > c0)
-          for (size_t s = 0; s < steps; ++s) {
-            const bool rootB = (side == CAPI_LEFT ? t.y : t.x) == t.z + s * t.c;
-            if (rootB && !B.contiguous()) CAPITAL_CHECK(capi_dlacpy(h, 0, B.rows, c1 - c0, B.p + c0 * B.ld, B.ld, bb[s].p + c0 * bb[s].ld, bb[s].ld));
-            bcast_axis(t, axB, s, bb[s].p + c0 * bb[s].ld, bb[s].rows * (c1 - c0), relay);
-          }
-        P.rec(EB + j);
-      }
-      P.main(); P.wait(ET);
-      for (int j = 0; j < nch; ++j) {
-        int64_t c0, c1;
-        chunk_range(N, nch, j, c0, c1);
+      P.whole_sent();
+      relay = relay_space(t, M * plan.widest(), ws);
+      const std::vector<view> bb = stream_chunks(t, P, axB, steps, B, plan, relay, ws);
+      P.resume();
+      P.products(plan, [&](int j, int64_t c0, int64_t c1) {
         P.wait(EB + j);
-        if (c1 > c0) {
-          double* Cj = Cout.p + c0 * Cout.ld;
-          for (size_t s = 0; s < steps; ++s) {
-            const double b0 = s ? 1.0 : 0.0;
-            if (side == CAPI_LEFT) {
-              CAPITAL_CHECK(capi_dtrmm_acc(h, side, uplo, trans, diag, M, c1 - c0, alpha, tt[s].p, tt[s].ld, bb[s].p + c0 * bb[s].ld, bb[s].ld, b0, Cj, Cout.ld));
-            } else {
-              // Cout[:, chunk] += alpha ( B[:, 0:c0] T[0:c0, chunk] + B[:, chunk] T[chunk, chunk] ): a rectangle above the chunk's triangle
-              if (c0 > 0)
-                CAPITAL_CHECK(capi_dgemm(h, CAPI_NOTRANS, CAPI_NOTRANS, M, c1 - c0, c0, alpha, bb[s].p, bb[s].ld, tt[s].p + c0 * tt[s].ld, tt[s].ld, b0, Cj, Cout.ld));
-              CAPITAL_CHECK(capi_dtrmm_acc(h, side, uplo, trans, diag, M, c1 - c0, alpha, tt[s].p + c0 + c0 * tt[s].ld, tt[s].ld, bb[s].p + c0 * bb[s].ld, bb[s].ld,
-                                           (c0 > 0 || s) ? 1.0 : 0.0, Cj, Cout.ld));
-            }
+        double* Cj = Cout.p + c0 * Cout.ld;
+        for (size_t s = 0; c1 > c0 && s < steps; ++s) {
+          const double b0 = s ? 1.0 : 0.0;
+          if (side == CAPI_LEFT) {
+            CAPITAL_CHECK(capi_dtrmm_acc(h, side, uplo, trans, diag, M, c1 - c0, alpha, tt[s].p, tt[s].ld, bb[s].p + c0 * bb[s].ld, bb[s].ld, b0, Cj, Cout.ld));
+          } else {
+            // Cout[:, chunk] += alpha ( B[:, 0:c0] T[0:c0, chunk] + B[:, chunk] T[chunk, chunk] ): a rectangle above the chunk's triangle
+            if (c0 > 0)
+              CAPITAL_CHECK(capi_dgemm(h, CAPI_NOTRANS, CAPI_NOTRANS, M, c1 - c0, c0, alpha, bb[s].p, bb[s].ld, tt[s].p + c0 * tt[s].ld, tt[s].ld, b0, Cj, Cout.ld));
+            CAPITAL_CHECK(capi_dtrmm_acc(h, side, uplo, trans, diag, M, c1 - c0, alpha, tt[s].p + c0 + c0 * tt[s].ld, tt[s].ld, bb[s].p + c0 * bb[s].ld, bb[s].ld,
+                                         (c0 > 0 || s) ? 1.0 : 0.0, Cj, Cout.ld));
           }
         }
-        P.rec(EC + j);
-      }
+      });
     }
-    if (t.c > 1) {
-      if (P.on) {
-        P.comm();
-        double* relay = relay_space(t, Cout.rows * cmax, ws);
-        double* half = depth_space(t, Cout.rows * cmax, ws);
-        for (int j = 0; j < nch; ++j) {
-          int64_t c0, c1;
-          chunk_range(N, nch, j, c0, c1);
-          P.wait(EC + j);
-          if (c1 > c0) allreduce_depth(t, Cout.p + c0 * Cout.ld, Cout.rows * (c1 - c0), half, relay);
-        }
-        P.rec(ER);
-        P.main(); P.wait(ER);
-      } else {
-        allreduce_view(t, Cout, ws);
-      }
-    } else if (P.on) {
-      P.main();
-    }
+    if (P.on) depth_sum(t, P, plan, Cout, [&](int64_t) { return Cout.rows; }, relay, ws);
+    else if (t.c > 1) allreduce_view(t, Cout, ws);
     ws.top = mark;
   }
 
@@ -432,11 +441,10 @@ public:
     }
     const int64_t mark = ws.top;
     const size_t steps = t.d > 1 ? t.d / t.c : 1;
-    // the pipeline is built for what cholinv issues: upper triangle, transposed form, one K-class per layer
+    // the pipeline is built for what cholinv issues: upper triangle, transposed form
     const bool piped = t.num_chunks > 0 && trans && uplo == CAPI_UPPER;
-    const int nch = piped ? chunk_count(t.num_chunks, N) : 1;
-    pipe P(piped && nch > 1);
-    enum { E0 = 0, EL = 1, EB = 2, EC = 70, ER = 140 };
+    const chunks plan{N, piped ? chunk_count(t.num_chunks, N) : 1};
+    pipe P(piped && plan.nch > 1);
     view acc = t.c > 1 ? view{ws.take(N * N), N, N, N} : C;
     if (!P.on) {
       if (t.d == 1) {
@@ -465,68 +473,33 @@ public:
       return;
     }
     // ---- pipelined: C(upper)[:, chunk] = alpha * sum over this layer's K-class steps of L_s[:, 0:c1]^T * R_s[:, chunk]; K x N, k-contiguous
-    int64_t k0 = 0, k1 = K;
-    std::vector<view> l(steps, Bx), r(steps, A);
+    //      (d == 1: nothing travels before the depth sum, layer z multiplies its slice [k0,k1) of the local K range)
     const bool sliced = (t.d == 1);
-    int64_t cmax = 0;
-    for (int j = 0; j < nch; ++j) { int64_t c0, c1; chunk_range(N, nch, j, c0, c1); cmax = std::max(cmax, c1 - c0); }
-    P.main(); P.rec(E0);
-    P.comm(); P.wait(E0);
-    if (sliced) {
-      kslice(K, t.c, t.z, k0, k1);
-    } else {
-      for (size_t s = 0; s < steps; ++s) {
-        l[s] = panel(t, AX_ROW, s, Bx, ws);
-        const bool rootR = t.y == t.z + s * t.c;
-        r[s] = view{(rootR && A.contiguous()) ? A.p : ws.take(A.count()), A.rows, A.rows, A.cols};
-      }
-    }
-    P.rec(EL);
-    double* relay = relay_space(t, std::max(A.rows, N) * cmax, ws);
-    for (int j = 0; j < nch; ++j) {
-      int64_t c0, c1;
-      chunk_range(N, nch, j, c0, c1);
-      if (!sliced && c1 > c0)
-        for (size_t s = 0; s < steps; ++s) {
-          const bool rootR = t.y == t.z + s * t.c;
-          if (rootR && !A.contiguous()) CAPITAL_CHECK(capi_dlacpy(h, 0, A.rows, c1 - c0, A.p + c0 * A.ld, A.ld, r[s].p + c0 * r[s].ld, r[s].ld));
-          bcast_axis(t, AX_COLUMN, s, r[s].p + c0 * r[s].ld, r[s].rows * (c1 - c0), relay);
-        }
-      P.rec(EB + j);
-    }
-    P.main(); P.wait(EL);
+    int64_t k0 = 0, k1 = K;
+    if (sliced) kslice(K, t.c, t.z, k0, k1);
+    std::vector<view> l(steps, Bx);
+    P.begin();
+    if (!sliced)
+      for (size_t s = 0; s < steps; ++s) l[s] = panel(t, AX_ROW, s, Bx, ws);
+    P.whole_sent();
+    double* relay = relay_space(t, std::max(A.rows, N) * plan.widest(), ws);             // (one buffer for stages 3 and 5)
+    const std::vector<view> r = stream_chunks(t, P, AX_COLUMN, sliced ? 0 : steps, A, plan, relay, ws);
+    P.resume();
     if (t.c > 1) capital::dev_zero(acc.p, acc.count());       // (the part below the computed trapezoids is folded into C as zeros)
-    for (int j = 0; j < nch; ++j) {
-      int64_t c0, c1;
-      chunk_range(N, nch, j, c0, c1);
+    P.products(plan, [&](int j, int64_t c0, int64_t c1) {
       P.wait(EB + j);
-      if (c1 > c0)
-        for (size_t s = 0; s < steps; ++s) {
-          const double bt = s ? 1.0 : (t.c > 1 ? 0.0 : beta);
-          const double* rj = r[s].p + k0 + c0 * r[s].ld;
-          if (c0 > 0)   // rows above the diagonal block of this chunk: a plain rectangle
-            CAPITAL_CHECK(capi_dgemm(h, CAPI_TRANS, CAPI_NOTRANS, c0, c1 - c0, k1 - k0, alpha, l[s].p + k0, l[s].ld, rj, r[s].ld, bt, acc.p + c0 * acc.ld, acc.ld));
-          CAPITAL_CHECK(capi_dgemmt(h, CAPI_UPPER, CAPI_TRANS, CAPI_NOTRANS, c1 - c0, k1 - k0, alpha, l[s].p + k0 + c0 * l[s].ld, l[s].ld, rj, r[s].ld, bt,
-                                    acc.p + c0 + c0 * acc.ld, acc.ld));
-        }
-      P.rec(EC + j);
-    }
-    if (t.c > 1) {
-      P.comm();
-      double* half = depth_space(t, acc.rows * cmax, ws);
-      for (int j = 0; j < nch; ++j) {
-        int64_t c0, c1;
-        chunk_range(N, nch, j, c0, c1);
-        P.wait(EC + j);
-        // (rows 0 .. c1 of the chunk's columns hold the computed part; the zeros below it are not sent)
-        if (c1 > c0) allreduce_cols(t, acc.p + c0 * acc.ld, acc.ld, c1, c1 - c0, half, relay, ws);
+      for (size_t s = 0; c1 > c0 && s < steps; ++s) {
+        const double bt = s ? 1.0 : (t.c > 1 ? 0.0 : beta);
+        const double* rj = r[s].p + k0 + c0 * r[s].ld;
+        if (c0 > 0)   // rows above the diagonal block of this chunk: a plain rectangle
+          CAPITAL_CHECK(capi_dgemm(h, CAPI_TRANS, CAPI_NOTRANS, c0, c1 - c0, k1 - k0, alpha, l[s].p + k0, l[s].ld, rj, r[s].ld, bt, acc.p + c0 * acc.ld, acc.ld));
+        CAPITAL_CHECK(capi_dgemmt(h, CAPI_UPPER, CAPI_TRANS, CAPI_NOTRANS, c1 - c0, k1 - k0, alpha, l[s].p + k0 + c0 * l[s].ld, l[s].ld, rj, r[s].ld, bt,
+                                  acc.p + c0 + c0 * acc.ld, acc.ld));
       }
-      P.rec(ER);
-      P.main(); P.wait(ER);
-      CAPITAL_CHECK(capi_dgeadd(h, 1, N, N, 1.0, acc.p, acc.ld, beta, C.p, C.ld));
-    } else {
-      P.main();
-    }
+    });
+    // (rows 0 .. c1 of a chunk's columns hold the computed part; the zeros below it are not sent)
+    depth_sum(t, P, plan, acc, [](int64_t c1) { return c1; }, relay, ws);
+    if (t.c > 1) CAPITAL_CHECK(capi_dgeadd(h, 1, N, N, 1.0, acc.p, acc.ld, beta, C.p, C.ld));
     ws.top = mark;
   }
 
@@ -561,7 +534,8 @@ public:
   }
   // compute(c0, c1) enqueues the kernels that finish output columns [c0, c1) in place at `base` (leading dimension ld); rows_of(c1) = how
   // many leading rows of those columns carry the result (all of them, or c1 for an upper-triangular output).  With num_chunks > 0 the
-  // exchange of chunk j (communication stream) runs beside the computation of chunk j + 1.
+  // exchange of chunk j (communication stream) runs beside the computation of chunk j + 1: a schedule of its own (per-layer broadcasts, no
+  // accumulator) on the chunk plan and the event slots of the pipeline above.
   template <typename CommType, typename Compute, typename RowsOf>
   static void colsplit_run(CommType&& t, int64_t N, bool triangular, double* base, int64_t ld, Compute&& compute, RowsOf&& rows_of, arena& ws) {
     capi_handle_t h = capital::handle();
@@ -571,33 +545,29 @@ public:
     for (size_t z = 0; z <= t.c; ++z) b[z] = colsplit_bound(N, t.c, z, triangular);
     for (size_t z = 0; z < t.c; ++z) widest = std::max(widest, b[z + 1] - b[z]);
     const int nch = t.num_chunks > 0 ? chunk_count(t.num_chunks, widest) : 1;
+    auto plan = [&](size_t z) { return chunks{b[z + 1] - b[z], nch}; };       // every layer's column range is cut into the same number of chunks
     pipe P(nch > 1);
-    enum { EC = 70, ER = 140 };
     double* tmp = nullptr;                                       // staging of a strided block (allocated once: it is used on the communication stream)
     int64_t tmp_need = 0;
     for (size_t z = 0; z < t.c; ++z)
-      for (int j = 0; j < nch; ++j) {
-        int64_t c0, c1;
-        chunk_range(b[z + 1] - b[z], nch, j, c0, c1);
+      plan(z).each([&](int, int64_t c0, int64_t c1) {
         const int64_t rows = rows_of(b[z] + c1);
         if (rows != ld) tmp_need = std::max(tmp_need, rows * (c1 - c0));
-      }
+      });
     if (tmp_need > 0) tmp = ws.take(tmp_need);
     P.main();
     for (int j = 0; j < nch; ++j) {
-      int64_t c0, c1;
-      chunk_range(b[t.z + 1] - b[t.z], nch, j, c0, c1);
-      if (c1 > c0) compute(b[t.z] + c0, b[t.z] + c1);
-      P.rec(EC + j);
+      const chunks::span r = plan(t.z).range(j);
+      if (!r.empty()) compute(b[t.z] + r.c0, b[t.z] + r.c1);
+      P.rec(pipe::EC + j);
     }
     P.comm();
     for (int j = 0; j < nch; ++j) {
-      P.wait(EC + j);
+      P.wait(pipe::EC + j);
       for (size_t z = 0; z < t.c; ++z) {
-        int64_t c0, c1;
-        chunk_range(b[z + 1] - b[z], nch, j, c0, c1);
-        if (c1 <= c0) continue;
-        const int64_t g0 = b[z] + c0, g1 = b[z] + c1, rows = rows_of(g1);
+        const chunks::span r = plan(z).range(j);
+        if (r.empty()) continue;
+        const int64_t g0 = b[z] + r.c0, g1 = b[z] + r.c1, rows = rows_of(g1);
         double* blk = base + g0 * ld;
         if (rows == ld) {
           CAPITAL_CHECK(capi_bcast(t.depth, blk, rows * (g1 - g0), (int)z));
@@ -608,12 +578,15 @@ public:
         }
       }
     }
-    P.rec(ER);
-    P.main(); P.wait(ER);
+    P.rec(pipe::ER);
+    P.main(); P.wait(pipe::ER);
     ws.top = mark;
   }
 
   enum { AX_ROW = 0, AX_COLUMN = 1 };
+  // is this rank the root of the broadcast along `axis` at K-class step s?  (layer z owns K-classes z, z + c, ...)
+  template <typename CommType>
+  static bool is_root(CommType&& t, int axis, size_t s) { return (axis == AX_ROW ? t.x : t.y) == t.z + s * t.c; }
 
   // ---- pair collectives: over every link of the node (capi_pairs_transfer, csrc/pair_paths.h) when the grid's rows / columns /
   //      depth fibres are pairs, else as RCCL calls on the sub-communicators ---------------------------------------------------------
@@ -631,13 +604,12 @@ public:
   // MPI_Bcast(row | column) of `count` doubles at `buf`, root = the member whose x (y) is this layer's K-class at step s (summa.hpp:185,193)
   template <typename CommType>
   static void bcast_axis(CommType&& t, int axis, size_t s, double* buf, int64_t count, double* relay) {
-    const size_t q = t.z + s * t.c;
     if (t.pairs_along(axis)) {
-      const bool root = (axis == AX_ROW ? t.x : t.y) == q;
+      const bool root = is_root(t, axis, s);
       const std::vector<int> dst = t.bcast_dst(axis, s);
       CAPITAL_CHECK(capi_pairs_transfer(t.world, dst.data(), root ? buf : nullptr, root ? nullptr : buf, count, relay));
     } else {
-      CAPITAL_CHECK(capi_bcast(axis == AX_ROW ? t.row : t.column, buf, count, (int)q));
+      CAPITAL_CHECK(capi_bcast(axis == AX_ROW ? t.row : t.column, buf, count, (int)(t.z + s * t.c)));
     }
   }
   // MPI_Allreduce(depth, SUM) in place (summa.hpp:236).  On a depth PAIR: each member keeps one half, the halves that are not kept
@@ -655,109 +627,106 @@ public:
     CAPITAL_CHECK(capi_pairs_transfer(t.world, dst.data(), keep, give, half, relay));
     if (count > c4) CAPITAL_CHECK(capi_allreduce_sum(t.depth, buf + c4, count - c4));     // (at most three trailing values)
   }
+  // sum over depth of the block v, in place; a strided block travels as a contiguous copy.  half_space / relay sized for v.count();
+  // the copy's arena space stays taken until the caller resets its mark: it lives on the communication stream of a pipelined multiply.
   template <typename CommType>
-  static void allreduce_depth(CommType&& t, double* buf, int64_t count, arena& ws) {
+  static void allreduce_view(CommType&& t, view v, double* half_space, double* relay, arena& ws) {
+    if (v.contiguous()) { allreduce_depth(t, v.p, v.count(), half_space, relay); return; }
+    capi_handle_t h = capital::handle();
+    double* tmp = ws.take(v.count());
+    CAPITAL_CHECK(capi_dlacpy(h, 0, v.rows, v.cols, v.p, v.ld, tmp, v.rows));
+    allreduce_depth(t, tmp, v.count(), half_space, relay);
+    CAPITAL_CHECK(capi_dlacpy(h, 0, v.rows, v.cols, tmp, v.rows, v.p, v.ld));
+  }
+  // the same with the landing and relay space from the arena, outside a pipeline (all of it is given back)
+  template <typename CommType>
+  static void allreduce_view(CommType&& t, view v, arena& ws) {
     const int64_t mark = ws.top;
-    double* half = depth_space(t, count, ws);
-    double* relay = t.pairs_in_depth() ? relay_space(t, count / 2 + 2, ws) : nullptr;
-    allreduce_depth(t, buf, count, half, relay);
+    double* half = depth_space(t, v.count(), ws);
+    double* relay = t.pairs_in_depth() ? relay_space(t, v.count() / 2 + 2, ws) : nullptr;
+    allreduce_view(t, v, half, relay, ws);
     ws.top = mark;
   }
-  // sum over depth of `rows` x `cols` values at p (leading dimension ld); a strided block travels as a contiguous copy
-  // (half_space / relay sized for rows * cols; arena space taken here stays taken until the caller resets its mark: the copies
-  //  live on the communication stream of a pipelined multiply)
-  template <typename CommType>
-  static void allreduce_cols(CommType&& t, double* p, int64_t ld, int64_t rows, int64_t cols, double* half_space, double* relay, arena& ws) {
-    if (rows == ld) { allreduce_depth(t, p, rows * cols, half_space, relay); return; }
-    capi_handle_t h = capital::handle();
-    double* tmp = ws.take(rows * cols);
-    CAPITAL_CHECK(capi_dlacpy(h, 0, rows, cols, p, ld, tmp, rows));
-    allreduce_depth(t, tmp, rows * cols, half_space, relay);
-    CAPITAL_CHECK(capi_dlacpy(h, 0, rows, cols, tmp, rows, p, ld));
-  }
 
+  // "Own block or staged copy": a block that travels is sent from / received into `landing` -- the root's own block if that is
+  // contiguous, arena space otherwise --, and the root of a strided block copies the columns [c0, c1) there before they go (`stage`).
+  static view landing(bool root, const view& mine, arena& ws) {
+    return view{(root && mine.contiguous()) ? mine.p : ws.take(mine.count()), mine.rows, mine.rows, mine.cols};
+  }
+  static void stage(bool root, const view& mine, const view& at, int64_t c0, int64_t c1) {
+    if (root && !mine.contiguous())
+      CAPITAL_CHECK(capi_dlacpy(capital::handle(), 0, mine.rows, c1 - c0, mine.p + c0 * mine.ld, mine.ld, at.p + c0 * at.ld, at.ld));
+  }
   // The panel a rank multiplies with: the root's own block (packed to contiguous if it is a strided view) broadcast
   // over `comm`.  Non-roots receive into arena memory.  Blocks have equal shapes on all ranks of a communicator.
-  static view panel(capi_comm_t comm, bool is_root, int root, const view& mine, arena& ws) {
+  static view panel(capi_comm_t comm, bool root, int root_rank, const view& mine, arena& ws) {
     int size = 1;
     CAPITAL_CHECK(capi_comm_size(comm, &size));
     if (size == 1) return mine;
-    view out{nullptr, mine.rows, mine.rows, mine.cols};
-    if (is_root && mine.contiguous()) {
-      out.p = mine.p;
-    } else {
-      out.p = ws.take(mine.count());
-      if (is_root) CAPITAL_CHECK(capi_dlacpy(capital::handle(), 0, mine.rows, mine.cols, mine.p, mine.ld, out.p, out.ld));
-    }
-    CAPITAL_CHECK(capi_bcast(comm, out.p, out.count(), root));
+    view out = landing(root, mine, ws);
+    stage(root, mine, out, 0, mine.cols);
+    CAPITAL_CHECK(capi_bcast(comm, out.p, out.count(), root_rank));
     return out;
   }
   // the same along an axis of the grid at K-class step s (multi-path on grids of pairs)
   template <typename CommType>
   static view panel(CommType&& t, int axis, size_t s, const view& mine, arena& ws) {
-    const size_t q = t.z + s * t.c;
-    const bool is_root = (axis == AX_ROW ? t.x : t.y) == q;
-    if (!t.pairs_along(axis)) return panel(axis == AX_ROW ? t.row : t.column, is_root, (int)q, mine, ws);
-    view out{nullptr, mine.rows, mine.rows, mine.cols};
-    if (is_root && mine.contiguous()) {
-      out.p = mine.p;
-    } else {
-      out.p = ws.take(mine.count());
-      if (is_root) CAPITAL_CHECK(capi_dlacpy(capital::handle(), 0, mine.rows, mine.cols, mine.p, mine.ld, out.p, out.ld));
-    }
+    const bool root = is_root(t, axis, s);
+    if (!t.pairs_along(axis)) return panel(axis == AX_ROW ? t.row : t.column, root, (int)(t.z + s * t.c), mine, ws);
+    view out = landing(root, mine, ws);
+    stage(root, mine, out, 0, mine.cols);
     const int64_t mark = ws.top;
     bcast_axis(t, axis, s, out.p, out.count(), relay_space(t, out.count(), ws));
     ws.top = mark;                                              // (relay space is reused in stream order)
     return out;
   }
-  // A TRIANGULAR operand travels packed (n(n+1)/2 doubles instead of n^2, the reference's Serialize policy on the wire,
-  // summa.hpp:147-148,216-217): the root packs, everyone unpacks the triangle into a full-stride buffer whose other half is
-  // never read (the kernels truncate each tile's k-range at the diagonal and mask the diagonal panels by selection).
+
+  // ---- triangles on the wire: n(n+1)/2 doubles instead of n^2 (the reference's Serialize policy, summa.hpp:147-148,216-217) ----------
+  static bool packed_comm() { return getenv("CAPITAL_NO_PACKED_COMM") == nullptr; }      // (read per transfer)
+  static int64_t tri_count(int64_t n) { return n * (n + 1) / 2; }
+  // the `uplo` triangle of the square block v -> tri_count(v.rows) packed doubles, and back into a full-stride block whose other half is
+  // left alone (no kernel reads it: the tile kernels truncate each tile's k-range at the diagonal and mask the diagonal panels by selection)
+  static void pack_tri(const view& v, int uplo, double* packed) {
+    const int64_t n = v.rows;
+    const int st = uplo == CAPI_UPPER ? CAPI_UPPERTRI : CAPI_LOWERTRI;
+    CAPITAL_CHECK(capi_serialize_shape(capital::handle(), st, CAPI_RECT, st, v.p, n, v.ld, packed, n, n, 0, n, 0, n, 0, n, 0, n));
+  }
+  static void unpack_tri(const double* packed, int uplo, const view& v) {
+    const int64_t n = v.rows;
+    const int st = uplo == CAPI_UPPER ? CAPI_UPPERTRI : CAPI_LOWERTRI;
+    CAPITAL_CHECK(capi_serialize_shape(capital::handle(), st, st, CAPI_RECT, packed, n, n, v.p, n, v.ld, 0, n, 0, n, 0, n, 0, n));
+  }
+  // A TRIANGULAR operand's panel: the root packs, everyone else unpacks into arena memory
   template <typename CommType>
   static view panel_tri(CommType&& t, int axis, size_t s, const view& mine, int uplo, arena& ws) {
     capi_comm_t comm = axis == AX_ROW ? t.row : t.column;
     int size = 1;
     CAPITAL_CHECK(capi_comm_size(comm, &size));
     if (size == 1) return mine;
-    static const bool off = getenv("CAPITAL_NO_PACKED_COMM") != nullptr;
-    if (off || mine.rows != mine.cols) return panel(t, axis, s, mine, ws);
-    capi_handle_t h = capital::handle();
-    const size_t q = t.z + s * t.c;
-    const bool is_root = (axis == AX_ROW ? t.x : t.y) == q;
-    const int64_t n = mine.rows, np = n * (n + 1) / 2;
-    const int st = uplo == CAPI_UPPER ? CAPI_UPPERTRI : CAPI_LOWERTRI;
+    if (!packed_comm() || mine.rows != mine.cols) return panel(t, axis, s, mine, ws);
+    const bool root = is_root(t, axis, s);
+    const int64_t n = mine.rows, np = tri_count(n);
     double* packed = ws.take(np);
-    if (is_root) CAPITAL_CHECK(capi_serialize_shape(h, st, CAPI_RECT, st, mine.p, n, mine.ld, packed, n, n, 0, n, 0, n, 0, n, 0, n));
+    if (root) pack_tri(mine, uplo, packed);
     {
       const int64_t mark = ws.top;
       bcast_axis(t, axis, s, packed, np, relay_space(t, np, ws));
       ws.top = mark;
     }
-    if (is_root) return mine;                                   // the root multiplies with its own block
+    if (root) return mine;                                      // the root multiplies with its own block
     view out{ws.take(n * n), n, n, n};
-    CAPITAL_CHECK(capi_serialize_shape(h, st, st, CAPI_RECT, packed, n, n, out.p, n, n, 0, n, 0, n, 0, n, 0, n));
+    unpack_tri(packed, uplo, out);
     return out;
   }
   // sum over depth of the `uplo` triangle of a contiguous n x n accumulator, packed on the wire
   template <typename CommType>
   static void allreduce_tri(CommType&& t, view acc, int uplo, arena& ws) {
-    static const bool off = getenv("CAPITAL_NO_PACKED_COMM") != nullptr;
-    if (off || acc.rows != acc.cols || !acc.contiguous()) { allreduce_depth(t, acc.p, acc.count(), ws); return; }
-    capi_handle_t h = capital::handle();
-    const int64_t n = acc.rows, np = n * (n + 1) / 2;
-    const int st = uplo == CAPI_UPPER ? CAPI_UPPERTRI : CAPI_LOWERTRI;
+    if (!packed_comm() || acc.rows != acc.cols || !acc.contiguous()) { allreduce_view(t, acc, ws); return; }
+    const int64_t np = tri_count(acc.rows);
     double* packed = ws.take(np);
-    CAPITAL_CHECK(capi_serialize_shape(h, st, CAPI_RECT, st, acc.p, n, n, packed, n, n, 0, n, 0, n, 0, n, 0, n));
-    allreduce_depth(t, packed, np, ws);
-    CAPITAL_CHECK(capi_serialize_shape(h, st, st, CAPI_RECT, packed, n, n, acc.p, n, n, 0, n, 0, n, 0, n, 0, n));
-  }
-  template <typename CommType>
-  static void allreduce_view(CommType&& t, view v, arena& ws) {
-    if (v.contiguous()) { allreduce_depth(t, v.p, v.count(), ws); return; }
-    double* tmp = ws.take(v.count());
-    CAPITAL_CHECK(capi_dlacpy(capital::handle(), 0, v.rows, v.cols, v.p, v.ld, tmp, v.rows));
-    allreduce_depth(t, tmp, v.count(), ws);
-    CAPITAL_CHECK(capi_dlacpy(capital::handle(), 0, v.rows, v.cols, tmp, v.rows, v.p, v.ld));
+    pack_tri(acc, uplo, packed);
+    allreduce_view(t, view{packed, np, np, 1}, ws);
+    unpack_tri(packed, uplo, acc);
   }
 };
 
