@@ -54,6 +54,7 @@ def bind(D):
     D.capital_cholinv_dims.argtypes = [_vp, C.POINTER(_i64)] + [C.POINTER(_int)] * 5
     D.capital_cholinv_stats.argtypes = [_vp] + [C.POINTER(_i64)] * 3
     D.capital_cholinv_set_trsm_mode.argtypes = [_vp, _int]
+    D.capital_cholinv_solve.argtypes = [_vp, _i64, _dp, _dp, _dp, _int]
     D.capital_cacqr_create.argtypes = [_i64, _i64] + [_int] * 8
     D.capital_cacqr_create.restype = _vp
     D.capital_cacqr_set_A.argtypes = [_vp, _dp]
@@ -166,6 +167,23 @@ class Cholinv:
         v = _dbl()
         _ck(self.D.capital_cholinv_residual(self.p, C.byref(v)), "residual")
         return v.value
+
+    def solve(self, B, refine=1, residual=True):
+        """A X = B on the factors of the last factor() (cholesky::cholinv::solve, one rank): products with the resident R^-1 -- block-wise with
+        R^-1_11, R^-1_22 and R_12 where complete_inv=0 skipped R^-1_12 -- or capi_dtrsm on R in TRSM mode, then `refine` steps of
+        fixed-precision refinement.  B: n x r.  Returns (X, resnorms): X n x r; resnorms[j] = ||b_j - A x_j||_2, or None with residual=False.
+        refine > 0 and residual read both triangles of A: A must be stored symmetric (generate(), or set_A of a symmetric array)."""
+        b = np.asfortranarray(B, dtype=np.float64)
+        if b.ndim == 1:
+            b = np.asfortranarray(b[:, None])
+        if b.ndim != 2 or b.shape[0] != self.n or b.shape[1] < 1:
+            raise DriverError(f"Cholinv.solve: B must be {self.n} x r with r >= 1, got {b.shape}")
+        r = b.shape[1]
+        X = np.zeros((self.n, r), order="F")
+        res = np.zeros(r) if residual else None
+        _ck(self.D.capital_cholinv_solve(self.p, r, b.ctypes.data_as(_dp), X.ctypes.data_as(_dp), res.ctypes.data_as(_dp) if residual else None,
+                                         int(refine)), "solve")
+        return X, res
 
     def _get(self, which):
         out = np.zeros((self.n_loc, self.n_loc), order="F")

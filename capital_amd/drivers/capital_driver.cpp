@@ -38,6 +38,7 @@ struct cholinv_problem {
   virtual void dims(int64_t* nloc, int* x, int* y, int* z, int* d, int* c) = 0;
   virtual void stats(int64_t* bc, int64_t* levels, int64_t* bcdim) = 0;
   virtual void set_trsm_mode(bool on) = 0;
+  virtual void solve(int64_t r, const double* B_host, double* X_host, double* resnorm_host, int refine) = 0;
 };
 
 template <class Alg>
@@ -76,6 +77,17 @@ struct cholinv_impl : cholinv_problem {
   }
   void stats(int64_t* bc, int64_t* levels, int64_t* bcdim) override { *bc = pack.num_base_cases; *levels = pack.num_levels; *bcdim = pack.bcDimension; }
   void set_trsm_mode(bool on) override { pack.solve_with_trsm = on; }
+  // A X = B on the factors of the last factor(): B_host n x r column-major, X_host receives n x r, resnorm_host (may be NULL: no residual
+  // pass) the r norms ||b_j - A x_j||_2
+  void solve(int64_t r, const double* B_host, double* X_host, double* resnorm_host, int refine) override {
+    if (r < 1 || !B_host || !X_host) throw std::invalid_argument("cholinv solve: r >= 1 right-hand sides, B and X expected");
+    MatrixType B(r, A.num_rows_global(), 1, 1);
+    B.from_host(B_host);
+    Alg::solve(A, B, pack, grid, refine, resnorm_host != nullptr);
+    auto x = pack.X.to_host();
+    std::memcpy(X_host, x.data(), sizeof(double) * x.size());
+    if (resnorm_host) std::memcpy(resnorm_host, pack.solve_residual_norms.data(), sizeof(double) * (size_t)r);
+  }
 };
 
 template <class SP, class IP>
@@ -224,6 +236,10 @@ int capital_cholinv_dims(void* p, int64_t* nloc, int* x, int* y, int* z, int* d,
 int capital_cholinv_stats(void* p, int64_t* bc, int64_t* levels, int64_t* bcdim) { return guarded([&] { ((cholinv_problem*)p)->stats(bc, levels, bcdim); }); }
 // TRSM mode (info::solve_with_trsm): potrf + block TRSM + SYRK recursion, no inverse formed (one GPU, or a d x d x c grid: potrf_rec_grid)
 int capital_cholinv_set_trsm_mode(void* p, int on) { return guarded([&] { ((cholinv_problem*)p)->set_trsm_mode(on != 0); }); }
+// A X = B on the factors (cholesky::cholinv::solve): after capital_cholinv_factor, one rank; resnorm_host_or_null == NULL skips the residual pass
+int capital_cholinv_solve(void* p, int64_t r, const double* B_host, double* X_host, double* resnorm_host_or_null, int refine) {
+  return guarded([&] { ((cholinv_problem*)p)->solve(r, B_host, X_host, resnorm_host_or_null, refine); });
+}
 int capital_cholinv_destroy(void* p) { return guarded([&] { capital::sync(); delete (cholinv_problem*)p; }); }
 
 void* capital_cacqr_create(int64_t m, int64_t n, int c, int variant, int layout, int num_chunks, int complete_inv, int split, int bc_mult, int serialize_) {

@@ -19,6 +19,11 @@
 #include "./../../matmult/summa/summa.h"
 #include "./policy.h"
 
+// The thin triangular product of solve() is a weak reference, as cacqr.h has its four: a stand-in of the C-ABI without it (the CPU rehearsal
+// shims of the test suite) still links and loads, factor() runs on it as before, and solve() refuses.
+#pragma weak capi_dtrmm_thin
+#pragma weak capi_dresid_ts
+
 namespace cholesky {
 
 template <class SerializePolicy = policy::cholinv::Serialize, class IntermediatesPolicy = policy::cholinv::SaveIntermediates,
@@ -68,6 +73,13 @@ public:
     DimensionType input_lead = 0;       // > 0: only this leading block of the input's left half was copied on the compute stream
     // trailing updates currently running beside the recursion on the bulk streams (single-GPU lookahead)
     int la_depth = 0;
+    // solve(): `factored` -- the last factor() came back with valid factors; top_split -- the order h1 of the leading block when the top level
+    // of the recursion split (0: it did not).  With complete_inv == 0 that is where R^-1 has its unformed block R^-1_12.
+    bool factored = false, factored_trsm = false;     // factored_trsm: the mode (solve_with_trsm) that factor() ran in
+    DimensionType top_split = 0;
+    // the solution X (n x r) and, when asked for, ||b_j - A x_j||_2 per right-hand side; n x CAPI_TS_MAX_RHS work blocks
+    matrix<ScalarType, DimensionType, rect> X, SolveW1, SolveW2, SolveRho, SolveD, SolveNorm2;
+    std::vector<double> solve_residual_norms;
   };
 
   template <typename MatrixType, typename ArgType, typename CommType>
@@ -77,7 +89,10 @@ public:
     static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::factor takes a rect-structured input block");
     if (!(args.split > 0) || args.dir != 'U') throw std::invalid_argument("cholinv: split > 0 and dir == 'U' required (cholinv.hpp:9)");
     if (CommInfo.d > 1 && CommInfo.d % CommInfo.c) throw std::invalid_argument("cholinv: c must divide d (or d == 1)");
-    if (args.solve_with_trsm) { factor_trsm(A, args, CommInfo); CRITTER_STOP(CI::factor); return; }
+    args.factored = false;
+    args.factored_trsm = args.solve_with_trsm;
+    args.top_split = 0;
+    if (args.solve_with_trsm) { factor_trsm(A, args, CommInfo); args.factored = true; CRITTER_STOP(CI::factor); return; }
     const U localDimension = A.num_rows_local(), globalDimension = A.num_rows_global();
     CAPITAL_CHECK(capi_stream_select(capital::handle(), 0));    // (a call that threw mid-way may have left another stream selected)
     CAPITAL_CHECK(capi_reset_info(capital::handle()));
@@ -119,6 +134,7 @@ public:
     args.early_split = 0;
     const bool will_split = !(((localDimension * (U)CommInfo.d) <= args.bcDimension) || (h1 < args.split));   // cholinv.hpp:93
     args.input_lead = 0;
+    args.top_split = will_split ? h1 : 0;
     if (will_split && h1 > 0 && h1 < ld) {
       capi_handle_t hh = capital::handle();
       // the left spine starts on the leading blocks: when the recursion halves cleanly down to `lead`, only that block is
@@ -196,6 +212,107 @@ public:
                               (args.potrf_info != 0 ? "non-positive pivot " + std::to_string(args.potrf_info) + " of a diagonal block"
                                                     : std::string("reported by ") + std::to_string(failed) + " other rank(s) of the grid") +
                               "); R and Rinv are not valid");
+    args.factored = true;
+  }
+
+  // A X = B on the factors factor(A, args, CommInfo) left, ONE rank: args.X (n x r) and, with `residual`, args.solve_residual_norms[j] =
+  // ||b_j - A x_j||_2.  B: matrix<double, int64_t, rect>(r, n, 1, 1).  The inverse is applied by products, CAPI_TS_MAX_RHS columns at a time
+  // (capi_dtrmm_thin: the factor is read once per product, packed or not, no copy of it is made):
+  //   complete inverse (complete_inv != 0, or the top level did not split):  Y = R^-T B, X = R^-1 Y
+  //   complete_inv == 0 and the top level split at h1 (R^-1_12 was never formed):
+  //       y1 = R11^-T b1,  y2 = R22^-T (b2 - R12^T y1),  x2 = R22^-1 y2,  x1 = R11^-1 (y1 - R12 x2)      -- the same bytes as the complete form
+  //   TRSM mode (no inverse exists): X = R^-1 R^-T B by capi_dtrsm on a full-storage R (Rfull where resident, or the rect structure)
+  // `refine` steps of fixed-precision refinement follow (rho = B - A X by capi_dresid_ts, X += solve(rho)): multiplying by an explicit inverse
+  // is not backward stable in general, one step restores a backward error at the level of u for kappa u < 1.  The refinement and the residual
+  // norms read BOTH triangles of A, where factor() reads the upper one only: with refine > 0 or residual, A must be stored symmetric
+  // (distribute_symmetric, or from_host of a symmetric array).  refine == 0 and residual == false do not touch A.
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void solve(const MatrixType& A, const MatrixType& B, ArgType& args, CommType&& CommInfo, int refine = 1, bool residual = true) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::solve takes rect-structured A and B");
+    constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
+    if (CommInfo.size > 1) throw std::logic_error("cholinv::solve is built for one rank: on a grid the factors are element-cyclic (factor there, solve on one rank)");
+    if (!&capi_dtrmm_thin || !&capi_dresid_ts) throw std::logic_error("cholinv: this C-ABI library has no capi_dtrmm_thin / capi_dresid_ts: no solve");
+    if (!args.factored || args.potrf_info != 0 || !args.R.filled() || (!args.solve_with_trsm && !args.Rinv.filled()))
+      throw std::logic_error("cholinv::solve: factor() has not run or did not succeed: there are no valid factors to solve with");
+    if (args.factored_trsm != args.solve_with_trsm)
+      throw std::logic_error("cholinv::solve: solve_with_trsm was changed after factor(): the resident factors are those of the other mode; factor() again");
+    const int64_t n = args.localDimension, r = B.num_columns_global();
+    if (r < 1 || B.num_rows_global() != n || B.num_rows_local() != n || A.num_rows_local() != n || A.num_columns_local() != n || refine < 0)
+      throw std::invalid_argument("cholinv::solve: B must be n x r with r >= 1 (matrix(r, n, 1, 1)), A the factored matrix, refine >= 0");
+    const double* Rfullp = nullptr;
+    if (args.solve_with_trsm) {
+      // (FlushIntermediates promises that no full-storage working image outlives factor(): none is relied on there, whatever is still allocated)
+      Rfullp = packed ? (IP::keep_arena && args.Rfull.filled() ? args.Rfull.data() : nullptr) : (const double*)args.R.data();
+      if (!Rfullp)
+        throw std::logic_error("cholinv::solve: TRSM mode with Serialize + FlushIntermediates leaves only the packed R, and capi_dtrsm takes full "
+                               "storage: use SaveIntermediates or NoSerialize with solve_with_trsm");
+    }
+    CRITTER_START(CI::solve);
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    const int64_t W = CAPI_TS_MAX_RHS, h1 = args.top_split;
+    const bool blocks = !args.solve_with_trsm && !args.complete_inv && h1 > 0 && h1 < n;
+    if (args.X.filled() && args.X.num_columns_local() != r) args.X._destroy_();
+    args.X._register_(r, n, 1, 1);
+    args.SolveW1._register_(W, n, 1, 1);
+    if (blocks) args.SolveW2._register_(W, n, 1, 1);
+    if (refine > 0) { args.SolveRho._register_(W, n, 1, 1); args.SolveD._register_(W, n, 1, 1); }
+    const double* Rp = (const double*)args.R.data();
+    const double* Ip = args.solve_with_trsm ? nullptr : (const double*)args.Rinv.data();
+    // the block of a factor whose first element is (i0, j0): a view into the packed triangle (ldt == 0, col0 = j0) or into the rect structure
+    auto thin = [&](const double* F, int shape, int trans, int64_t i0, int64_t j0, int64_t m, int64_t k, int64_t rb, double alpha, const double* Bp,
+                    double beta, double* Cp) {
+      const double* Tp = packed ? F + j0 * (j0 + 1) / 2 + i0 : F + i0 + j0 * n;
+      CAPITAL_CHECK(capi_dtrmm_thin(h, shape, trans, m, k, rb, alpha, Tp, packed ? 0 : n, packed ? j0 : 0, Bp, n, beta, Cp, n));
+    };
+    // Xo (n x rb, ld n) <- A^-1 Bi; Bi is not written and Xo != Bi
+    auto apply = [&](const double* Bi, double* Xo, int64_t rb) {
+      double* w1 = args.SolveW1.data();
+      if (args.solve_with_trsm) {
+        CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));
+        CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_TRANS, CAPI_NONUNIT, n, rb, 1.0, Rfullp, n, Xo, n));
+        CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, n, rb, 1.0, Rfullp, n, Xo, n));
+      } else if (!blocks) {
+        thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, 0, 0, n, n, rb, 1.0, Bi, 0.0, w1);
+        thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, 0, 0, n, n, rb, 1.0, w1, 0.0, Xo);
+      } else {
+        const int64_t h2 = n - h1;
+        double* w2 = args.SolveW2.data();
+        thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, 0, 0, h1, h1, rb, 1.0, Bi, 0.0, w1);                          // y1 = R11^-T b1
+        CAPITAL_CHECK(capi_dlacpy(h, 0, h2, rb, Bi + h1, n, w2 + h1, n));
+        thin(Rp, CAPI_RECT, CAPI_TRANS, 0, h1, h1, h2, rb, -1.0, w1, 1.0, w2 + h1);                      // b2 - R12^T y1
+        thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, h1, h1, h2, h2, rb, 1.0, w2 + h1, 0.0, w1 + h1);             // y2 = R22^-T (..)
+        thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, h1, h1, h2, h2, rb, 1.0, w1 + h1, 0.0, Xo + h1);           // x2 = R22^-1 y2
+        thin(Rp, CAPI_RECT, CAPI_NOTRANS, 0, h1, h1, h2, rb, -1.0, Xo + h1, 1.0, w1);                    // y1 - R12 x2
+        thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, 0, 0, h1, h1, rb, 1.0, w1, 0.0, Xo);                       // x1 = R11^-1 (..)
+      }
+    };
+    for (int64_t j = 0; j < r; j += W) {
+      const int64_t rb = std::min(W, r - j);
+      double* Xj = args.X.data() + j * n;
+      const double* Bj = B.data() + j * n;
+      apply(Bj, Xj, rb);
+      for (int it = 0; it < refine; ++it) {
+        CAPITAL_CHECK(capi_dresid_ts(h, n, n, rb, A.data(), n, Xj, n, Bj, n, args.SolveRho.data(), n, nullptr));
+        apply(args.SolveRho.data(), args.SolveD.data(), rb);
+        CAPITAL_CHECK(capi_dgeadd(h, 0, n, rb, 1.0, args.SolveD.data(), n, 1.0, Xj, n));
+      }
+    }
+    args.solve_residual_norms.clear();
+    if (residual) {
+      if (args.SolveNorm2.filled() && args.SolveNorm2.num_columns_local() != r) args.SolveNorm2._destroy_();
+      args.SolveNorm2._register_(r, 1, 1, 1);
+      for (int64_t j = 0; j < r; j += W)
+        CAPITAL_CHECK(capi_dresid_ts(h, n, n, std::min(W, r - j), A.data(), n, args.X.data() + j * n, n, B.data() + j * n, n, nullptr, 0,
+                                     args.SolveNorm2.data() + j));
+      args.solve_residual_norms = args.SolveNorm2.to_host();
+      for (double& v : args.solve_residual_norms) v = std::sqrt(v);
+    }
+    if (!IP::keep_arena) {
+      capital::sync();
+      args.SolveW1._destroy_(); args.SolveW2._destroy_(); args.SolveRho._destroy_(); args.SolveD._destroy_();
+    }
+    CRITTER_STOP(CI::solve);
   }
 
   // ---- TRSM mode -----------------------------------------------------------------------------------------------------------

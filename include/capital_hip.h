@@ -147,6 +147,22 @@ int capi_dgemtn_ts(capi_handle_t h, int64_t m, int64_t n, int64_t r, double alph
  * Rout == B: in place; colnorm2 == NULL: the residual alone; m == 0: colnorm2 <- 0. */
 int capi_dresid_ts(capi_handle_t h, int64_t m, int64_t n, int64_t r, const double* A, int64_t lda, const double* X, int64_t ldx,
                    const double* B, int64_t ldb, double* Rout, int64_t ldr, double* colnorm2);
+/* ---- a (packed) triangle or rectangle times a thin block: solves on the cholinv factors (cholesky::cholinv::solve).  Not in the reference:
+ * src/alg/cholesky/cholinv/cholinv.hpp stops at R and R^-1.
+ * C <- alpha * op(T) * B + beta * C for a thin B: 1 <= r <= CAPI_TS_MAX_RHS columns (more: CAPI_EINVAL, nothing is touched).
+ * T is an m x n block of which either all (shape CAPI_RECT) or the upper triangle incl. the diagonal (CAPI_UPPERTRI, m == n;
+ * nothing below the diagonal is read) takes part.
+ * ldt >= m: column-major.  ldt == 0: the block lies inside a PACKED upper triangle (structure.h uppertri: column x of the
+ * triangle starts at x (x + 1) / 2); T points at the block's first element and col0 is the triangle's column index of the block's
+ * first column, so block column j starts at T + (col0 + j)(col0 + j + 1) / 2 - col0 (col0 + 1) / 2.
+ * trans == CAPI_NOTRANS: C is m x r, B n x r.  CAPI_TRANS: C is n x r, B m x r.  C must not alias B.  beta == 0: C is not read.
+ * m == 0 or n == 0: C <- beta C.  T is read from HBM once per call; partial sums are combined in a fixed order (bit-identical runs, no atomics).
+ * Workspace: (slices + ceil(lines / 256)) x 256 x (16 or 32) doubles of the handle's workspace, lines = the rows of C and slices <= 256 -- 32 MiB
+ * for a triangle of order 65536, but 1 GiB for 2^22 output lines at r > 16: the call is built for the factors' shapes, not for tall panels
+ * (those have capi_dgemtn_ts / capi_dresid_ts).  B must be finite where T's triangle is not: inside the 32 x 32 parts that the diagonal crosses
+ * the entries below the diagonal take part as zeros (0 * B(k)), so a NaN or Inf in B reaches output lines that it does not belong to. */
+int capi_dtrmm_thin(capi_handle_t h, int shape, int trans, int64_t m, int64_t n, int64_t r, double alpha,
+                    const double* T, int64_t ldt, int64_t col0, const double* B, int64_t ldb, double beta, double* C, int64_t ldc);
 /* LAPACKE_dgeqrf / LAPACKE_dorgqr behind lapack::engine::_geqrf / _orgqr (lapack/interface.hpp:60-88; the reference has
  * the slots but no caller -- CholeskyQR2 is its QR).  Householder QR, LAPACK storage: R in the upper triangle, the
  * reflectors v_j (unit first entry implied) below it, tau[min(m,n)] on the DEVICE.  capi_dorgqr overwrites A (m x n,

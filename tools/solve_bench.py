@@ -1,0 +1,170 @@
+"""The thin triangular product behind cholesky::cholinv::solve on one GPU, on synthetic triangles (no factorization), measured alternately in
+the same process:
+
+  (a) capi_dtrmm_thin on the operand as it lies: packed or full storage, NOTRANS and TRANS, the CAPI_UPPERTRI form on the whole triangle and
+      the CAPI_RECT form on its top right quarter (the R12 block of a split at n / 2)
+  (b) the device copy of tools/hbm_copy_bench.py (b.copy_(a)) sized to MOVE the triangle's bytes (a copy of N bytes moves 2 N)
+  (c) the route through the earlier entry points: capi_serialize to full storage where the operand is packed, plus capi_dtrmm_oop on r columns
+
+for n = 16384 and 32768 and r = 1, 8, 32: warm-up, then `--reps` alternating rounds, median and min..max.  With --e2e N one Cholinv.solve
+(config 2's policies: complete_inv = 0, split = 1, Serialize) beside its factor().  The parent process makes no GPU call: every order runs in a
+child of its own under a time limit, and a failed child ends the run.
+
+    python tools/solve_bench.py [--reps 9] [--orders 16384,32768] [--e2e 32768] [--limit 300]"""
+import argparse
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def child(n, reps, warmup):
+    import ctypes as C
+    import torch
+    from capital_amd import capi
+    h = capi.Handle(0)
+    dev = "cuda:0"
+    g = torch.Generator(device=dev).manual_seed(1)
+    p = capi.ptr
+    # column-major n x n upper triangle (zeros below), its packed image, and the scratch that route (c) unpacks into
+    Tf = torch.empty((n, n), dtype=torch.float64, device=dev)
+    for j0 in range(0, n, 4096):                                          # (row j of the tensor is column j of the matrix)
+        blk = torch.randn((min(4096, n - j0), n), dtype=torch.float64, device=dev, generator=g) * (1.0 / n ** 0.5)
+        Tf[j0:j0 + blk.shape[0]] = torch.tril(blk, diagonal=j0)
+    np_ = n * (n + 1) // 2
+    Tp = torch.empty(np_, dtype=torch.float64, device=dev)
+    h.call("capi_serialize", capi.RECT, capi.UPPERTRI, p(Tf), n, n, p(Tp), n, n, 0, n, 0, n, 0, n, 0, n)
+    scratch = torch.zeros((n, n), dtype=torch.float64, device=dev)
+    h.sync()
+    ms = C.c_float()
+    h2 = n // 2
+
+    def timed(fn):
+        h.call("capi_timer_start")
+        fn()
+        h.call("capi_timer_stop_ms", C.byref(ms))
+        return ms.value
+
+    def fmt(ts):
+        return f"{statistics.median(ts):8.3f} ms [{min(ts):.3f} .. {max(ts):.3f}]"
+
+    def thin(shape, trans, m, k, r, T, ldt, col0, B, C_):
+        h.call("capi_dtrmm_thin", shape, trans, m, k, r, 1.0, T, ldt, col0, p(B), n, 0.0, p(C_), n)
+
+    def unpack():
+        h.call("capi_serialize", capi.UPPERTRI, capi.RECT, p(Tp), n, n, p(scratch), n, n, 0, n, 0, n, 0, n, 0, n)
+
+    def oop(trans, T, B, C_, r):
+        h.call("capi_dtrmm_oop", capi.LEFT, capi.UPPER, trans, capi.NONUNIT, n, r, 1.0, T, n, p(B), n, p(C_), n)
+
+    print(f"== n = {n}: the triangle is {8 * np_ / 1e9:.2f} GB packed, its quarter rectangle {8 * h2 * h2 / 1e9:.2f} GB; {reps} alternating rounds "
+          f"after {warmup} warm-up rounds; capi version {h.L.capi_version()}", flush=True)
+    for r in (1, 8, 32):
+        B = torch.randn((r, n), dtype=torch.float64, device=dev, generator=g)
+        Ca, Cc = capi.zeros(n, r), capi.zeros(n, r)
+        csrc = torch.empty(np_ // 2, dtype=torch.float64, device=dev).normal_()
+        cdst = torch.empty_like(csrc)
+        rect_p = p(Tp) + 8 * (h2 * (h2 + 1) // 2)                         # element (0, h2) of the packed triangle
+        rect_f = p(Tf) + 8 * h2 * n
+        steps = {}
+        for tn, t in (("N", capi.NOTRANS), ("T", capi.TRANS)):
+            steps[f"a.tri_{tn}.packed"] = lambda t=t: thin(capi.UPPERTRI, t, n, n, r, p(Tp), 0, 0, B, Ca)
+            steps[f"c.tri_{tn}.packed"] = lambda t=t: (unpack(), oop(t, p(scratch), B, Cc, r))
+            steps[f"a.tri_{tn}.full"] = lambda t=t: thin(capi.UPPERTRI, t, n, n, r, p(Tf), n, 0, B, Ca)
+            steps[f"c.tri_{tn}.full"] = lambda t=t: oop(t, p(Tf), B, Cc, r)
+            steps[f"a.rect_{tn}.packed"] = lambda t=t: thin(capi.RECT, t, h2, h2, r, rect_p, 0, h2, B, Ca)
+            steps[f"a.rect_{tn}.full"] = lambda t=t: thin(capi.RECT, t, h2, h2, r, rect_f, n, 0, B, Ca)
+        steps["copy"] = lambda: cdst.copy_(csrc)
+        times = {k: [] for k in steps}
+        for i in range(warmup + reps):
+            for k, fn in steps.items():
+                tm = timed(fn)
+                if i >= warmup:
+                    times[k].append(tm)
+        # the two routes computed the same thing (the last tri pair that ran into Ca and Cc: TRANS, full storage)
+        thin(capi.UPPERTRI, capi.TRANS, n, n, r, p(Tp), 0, 0, B, Ca)
+        oop(capi.TRANS, p(Tf), B, Cc, r)
+        h.sync()
+        d = (Ca - Cc).abs().max().item() / max(Cc.abs().max().item(), 1e-300)
+        print(f"-- r = {r}:  max |C_a - C_c| / max |C_c| = {d:.2e}")
+        med = {k: statistics.median(v) for k, v in times.items()}
+        for k in steps:
+            extra = ""
+            if k.startswith("a.tri"):
+                c = "c" + k[1:]
+                extra = f"   copy / (a) = {med['copy'] / med[k]:.2f}   (c) / (a) = {med[c] / med[k]:.2f}   min (c) / max (a) = {min(times[c]) / max(times[k]):.2f}"
+            elif k.startswith("a.rect"):
+                extra = f"   {8 * h2 * h2 / med[k] / 1e9:.2f} TB/s"
+            print(f"   {k:20s} {fmt(times[k])}{extra}")
+        print(f"   the copy moves {8 * np_ / 1e9:.2f} GB: {8 * np_ / med['copy'] / 1e9:.2f} TB/s at its median", flush=True)
+        del B, Ca, Cc, csrc, cdst
+    h.close()
+
+
+def e2e(n):
+    import numpy as np
+    from capital_amd import driver
+    driver.init(0, 0, 1, None, use_torch_stream=False)
+    try:
+        pr = driver.Cholinv(n, c=1, complete_inv=0, split=1, bc_mult=0 if n <= 2048 else -(max(n // 2048, 2).bit_length() - 1))
+        pr.generate()
+        tf, ts = [], {}
+        for _ in range(3):
+            t0 = time.perf_counter()
+            pr.factor()
+            driver.sync()
+            tf.append((time.perf_counter() - t0) * 1e3)
+        rng = np.random.default_rng(0)
+        for r in (1, 32):
+            B = np.asfortranarray(rng.standard_normal((n, r)))
+            for refine, residual in ((0, False), (1, True)):
+                v = []
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    X, res = pr.solve(B, refine=refine, residual=residual)
+                    v.append((time.perf_counter() - t0) * 1e3)
+                ts[(r, refine)] = (min(v), None if res is None else float(res.max()))
+        print(f"== end to end, n = {n}, {pr.stats()}: factor() {min(tf):.1f} ms (best of 3, wall clock)")
+        for (r, refine), (t, res) in ts.items():
+            print(f"   Cholinv.solve r = {r:2d} refine = {refine}: {t:8.1f} ms wall clock incl. the host copies of B and X"
+                  + (f", max ||b - A x|| = {res:.2e}" if res is not None else ""), flush=True)
+        pr.close()
+    finally:
+        driver.finalize()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--orders", default="16384,32768")
+    ap.add_argument("--e2e", type=int, default=0, help="order of one end-to-end factor() + solve (0: none)")
+    ap.add_argument("--limit", type=int, default=300, help="seconds per child")
+    ap.add_argument("--child", default=None)
+    a = ap.parse_args()
+    if a.child:
+        if a.child.startswith("e2e:"):
+            e2e(int(a.child[4:]))
+        else:
+            child(int(a.child), a.reps, a.warmup)
+        return 0
+    jobs = [o for o in a.orders.split(",") if o] + ([f"e2e:{a.e2e}"] if a.e2e else [])
+    for job in jobs:
+        try:
+            rc = subprocess.run([sys.executable, "-u", os.path.abspath(__file__), "--child", job, "--reps", str(a.reps), "--warmup", str(a.warmup)],
+                                timeout=a.limit).returncode
+        except subprocess.TimeoutExpired:
+            print(f"{job}: no result within {a.limit} s; stopping", flush=True)
+            return 124
+        if rc != 0:
+            print(f"{job}: the child ended with status {rc}; stopping", flush=True)
+            return rc
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
