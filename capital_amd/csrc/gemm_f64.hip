@@ -42,28 +42,15 @@ using gemm_plan::BK, gemm_plan::SK;   // 16-deep k-panels; [row][k] layout: row 
 // Two tile sizes share the code: TS = 128 (4x4 MFMA tiles per wave) for large outputs, TS = 64 (2x2 per wave, 4
 // workgroups per CU) when a 128-tiling would leave CUs idle (the small levels of the recursion).
 template <int TS> struct tile_cfg {
-  static constexpr int SR = TS + 8;                 // [k][row] layout: k-row stride in doubles
-  static constexpr int TILE_LDS = TS * SK;          // >= BK*SR
+  static constexpr int TILE_LDS = TS * SK;          // one operand panel, [row][k]
   static constexpr int STAGE_LDS = 2 * TILE_LDS;
   static constexpr int NQ = TS / 32;                // 16-byte pieces per thread per operand panel
   static constexpr int SUB = TS / 32;               // MFMA tiles per wave per dimension
 };
 constexpr int GROUP_M = 8;
-#ifndef CAPI_STORE_IN_SHADOW
-#define CAPI_STORE_IN_SHADOW 1
-#endif
-constexpr bool STORE_IN_SHADOW = CAPI_STORE_IN_SHADOW;
-#ifndef CAPI_LOADS_IN_SHADOW
-#define CAPI_LOADS_IN_SHADOW 1
-#endif
-constexpr bool LOADS_IN_SHADOW_ON = CAPI_LOADS_IN_SHADOW;
 // A row-contiguous operand ([k][row] in HBM) is transposed while it is staged, so that LDS holds every operand [row][k] and all
 // four variants run the k-contiguous variant's inner loop (16-byte fragment reads, the pinned schedule).
-#ifndef CAPI_TRANSPOSE_STAGE
-#define CAPI_TRANSPOSE_STAGE 1
-#endif
-constexpr bool TRANSPOSE_STAGE = CAPI_TRANSPOSE_STAGE;
-// thread -> element map of a row-contiguous operand's panel when it is staged transposed: piece q of thread tid is rows
+// thread -> element map of a row-contiguous operand's panel: piece q of thread tid is rows
 // rc_r, rc_r + 1 at k = rc_k.  A wave instruction covers 16 rows x 8 k: eight whole 128-byte lines on the way in, and
 // (rows 18 doubles apart in LDS) bank pairs (8 rp + 2 k) mod 64 on the way out -- two-way conflicts at most.
 template <int TS> __device__ __forceinline__ int rc_r(int tid, int q) { return 16 * ((tid >> 6) * (TS / 64) + (q >> 1)) + 2 * (tid & 7); }
@@ -139,11 +126,10 @@ __device__ __forceinline__ void panel_load(const double* __restrict__ X, int64_t
       v[q] = val;
     }
   } else {  // element (r,k) at X[r + k*ld]
-    const int rp = tid & (TS / 2 - 1), kb = tid / (TS / 2);
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-      const int r = r0 + (TRANSPOSE_STAGE ? rc_r<TS>(tid, q) : 2 * rp);
-      const int k = k0 + (TRANSPOSE_STAGE ? rc_k(tid, q) : kb + (512 / TS) * q);
+      const int r = r0 + rc_r<TS>(tid, q);
+      const int k = k0 + rc_k(tid, q);
       d2_t val = {0.0, 0.0};
       if (k < kend) {
         const double* p = X + (int64_t)k * ld + r;
@@ -179,9 +165,9 @@ __device__ __forceinline__ void panel_mask(int r0, int k0, int tid, bool keep_ge
       k[0] = k0 + 2 * (tid & 7);
       k[1] = k[0] + 1;
     } else {
-      r[0] = r0 + (TRANSPOSE_STAGE ? rc_r<TS>(tid, q) : 2 * (tid & (TS / 2 - 1)));
+      r[0] = r0 + rc_r<TS>(tid, q);
       r[1] = r[0] + 1;
-      k[0] = k[1] = k0 + (TRANSPOSE_STAGE ? rc_k(tid, q) : tid / (TS / 2) + (512 / TS) * q);
+      k[0] = k[1] = k0 + rc_k(tid, q);
     }
     double e0 = v[q].x, e1 = v[q].y;
     if (keep_ge ? (k[0] < r[0]) : (k[0] > r[0])) e0 = 0.0;
@@ -197,38 +183,24 @@ __device__ __forceinline__ void panel_mask(int r0, int k0, int tid, bool keep_ge
 
 template <int TS, bool KC>
 __device__ __forceinline__ void panel_store(double* __restrict__ L, int tid, const d2_t (&v)[TS / 32]) {
-  constexpr int SR = tile_cfg<TS>::SR;
   if (KC) {
     const int kp = tid & 7, rb = tid >> 3;
 #pragma unroll
     for (int q = 0; q < TS / 32; ++q) *(d2_t*)&L[(rb + 32 * q) * SK + 2 * kp] = v[q];
-  } else if (TRANSPOSE_STAGE) {
+  } else {
 #pragma unroll
     for (int q = 0; q < TS / 32; ++q) {
       double* d = &L[rc_r<TS>(tid, q) * SK + rc_k(tid, q)];
       d[0] = v[q].x;
       d[SK] = v[q].y;
     }
-  } else {
-    const int rp = tid & (TS / 2 - 1), kb = tid / (TS / 2);
-#pragma unroll
-    for (int q = 0; q < TS / 32; ++q) *(d2_t*)&L[(kb + (512 / TS) * q) * SR + 2 * rp] = v[q];
   }
 }
 
 // fragment for MFMA k-steps 2u and 2u+1 of 16-row sub-block `row` (panel row index of this lane).
 // k-step s = 2u+e of lane group g = lane>>4 consumes physical k = 8u + 2g + e in BOTH operands.
-template <int TS, bool KC>
 __device__ __forceinline__ d2_t frag_read(const double* __restrict__ L, int row, int u, int g) {
-  constexpr int SR = tile_cfg<TS>::SR;
-  if (KC || TRANSPOSE_STAGE) {
-    return *(const d2_t*)&L[row * SK + 8 * u + 2 * g];
-  } else {
-    d2_t f;
-    f.x = L[(8 * u + 2 * g) * SR + row];
-    f.y = L[(8 * u + 2 * g + 1) * SR + row];
-    return f;
-  }
+  return *(const d2_t*)&L[row * SK + 8 * u + 2 * g];
 }
 
 // One k-step (4 deep) of the wave's SUB x SUB MFMA tiles.  `keep` has one bit per (a,b) sub-tile: sub-tiles that are
@@ -327,10 +299,7 @@ __device__ __forceinline__ void trmm_tile_of(const GemmArgs& p, int r, int& ti, 
 template <int TS, bool AK, bool BKC>
 __global__ __launch_bounds__(NTHREADS, TS == 128 ? 2 : 4) void dgemm_tile_kernel(const GemmArgs p) {
   constexpr int BM = TS, BN = TS, SUB = tile_cfg<TS>::SUB, NQ = tile_cfg<TS>::NQ;
-  // the fully pinned iteration schedule counts 16-byte fragment reads: both operands k-contiguous (measured: +1.5 % there,
-  // -3 % on the variants whose row-contiguous operand is read in 8-byte pieces)
-  constexpr bool LOADS_IN_SHADOW = LOADS_IN_SHADOW_ON && ((AK && BKC) || TRANSPOSE_STAGE);
-  constexpr int NW = NQ * ((AK || !TRANSPOSE_STAGE ? 1 : 2) + (BKC || !TRANSPOSE_STAGE ? 1 : 2));   // LDS stores of one staging pass
+  constexpr int NW = NQ * ((AK ? 1 : 2) + (BKC ? 1 : 2));   // LDS stores of one staging pass (a transposed piece is two 8-byte stores)
   constexpr int TILE_LDS = tile_cfg<TS>::TILE_LDS, STAGE_LDS = tile_cfg<TS>::STAGE_LDS;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int tid = threadIdx.x;
@@ -380,16 +349,14 @@ __global__ __launch_bounds__(NTHREADS, TS == 128 ? 2 : 4) void dgemm_tile_kernel
   // per-thread source of the fast path (see panel_load for the thread -> element map)
   const bool interior = (i0 + BM <= p.M) && (j0 + BN <= p.N) && p.a_vec && p.b_vec;
   const double* fa = AK ? p.A + (int64_t)(i0 + (tid >> 3)) * p.lda + klo + 2 * (tid & 7)
-                     : TRANSPOSE_STAGE ? p.A + (int64_t)(klo + rc_k(tid, 0)) * p.lda + i0 + rc_r<TS>(tid, 0)
-                                       : p.A + (int64_t)(klo + tid / (TS / 2)) * p.lda + i0 + 2 * (tid & (TS / 2 - 1));
+                     : p.A + (int64_t)(klo + rc_k(tid, 0)) * p.lda + i0 + rc_r<TS>(tid, 0);
   const double* fb = BKC ? p.B + (int64_t)(j0 + (tid >> 3)) * p.ldb + klo + 2 * (tid & 7)
-                     : TRANSPOSE_STAGE ? p.B + (int64_t)(klo + rc_k(tid, 0)) * p.ldb + j0 + rc_r<TS>(tid, 0)
-                                       : p.B + (int64_t)(klo + tid / (TS / 2)) * p.ldb + j0 + 2 * (tid & (TS / 2 - 1));
+                     : p.B + (int64_t)(klo + rc_k(tid, 0)) * p.ldb + j0 + rc_r<TS>(tid, 0);
   // piece q of the fast path lies (q & 1) qsa + (q >> 1) qsa2 elements behind piece 0
-  const int64_t qsa = AK ? 32 * p.lda : TRANSPOSE_STAGE ? 8 * p.lda : (512 / TS) * p.lda;
-  const int64_t qsa2 = AK ? 64 * p.lda : TRANSPOSE_STAGE ? 16 : 2 * (512 / TS) * p.lda;
-  const int64_t qsb = BKC ? 32 * p.ldb : TRANSPOSE_STAGE ? 8 * p.ldb : (512 / TS) * p.ldb;
-  const int64_t qsb2 = BKC ? 64 * p.ldb : TRANSPOSE_STAGE ? 16 : 2 * (512 / TS) * p.ldb;
+  const int64_t qsa = AK ? 32 * p.lda : 8 * p.lda;
+  const int64_t qsa2 = AK ? 64 * p.lda : 16;
+  const int64_t qsb = BKC ? 32 * p.ldb : 8 * p.ldb;
+  const int64_t qsb2 = BKC ? 64 * p.ldb : 16;
   const int64_t ksa = AK ? kstep : (int64_t)kstep * p.lda, ksb = BKC ? kstep : (int64_t)kstep * p.ldb;
 
   // triangular output: on a diagonal tile the sub-tiles lying entirely in the unwanted triangle are never computed
@@ -435,7 +402,7 @@ __global__ __launch_bounds__(NTHREADS, TS == 128 ? 2 : 4) void dgemm_tile_kernel
     if (FAST) {
       fa += ksa;
       fb += ksb;
-      if (LOADS_IN_SHADOW) __builtin_amdgcn_s_setprio(1);     // one scheduling region from here to the end of the MFMAs
+      __builtin_amdgcn_s_setprio(1);     // one scheduling region from here to the end of the MFMAs
       panel_load_fast<TS>(fa, qsa, qsa2, ra);
       panel_load_fast<TS>(fb, qsb, qsb2, rb);       // (on a shared diagonal tile this re-reads A's panel: cache hit, never staged)
     } else if (more) {
@@ -471,34 +438,32 @@ __global__ __launch_bounds__(NTHREADS, TS == 128 ? 2 : 4) void dgemm_tile_kernel
     for (int u = 0; u < 2; ++u) {
       d2_t af[SUB], bf[SUB];
 #pragma unroll
-      for (int a = 0; a < SUB; ++a) af[a] = frag_read<TS, AK>(La, wm * (TS / 2) + a * 16 + r16, u, g);
+      for (int a = 0; a < SUB; ++a) af[a] = frag_read(La, wm * (TS / 2) + a * 16 + r16, u, g);
 #pragma unroll
-      for (int b = 0; b < SUB; ++b) bf[b] = frag_read<TS, BKC>(Lb, wn * (TS / 2) + b * 16 + r16, u, g);
-      if (!(FAST && LOADS_IN_SHADOW)) __builtin_amdgcn_s_setprio(1);      // keeps the cluster contiguous (+1 % measured)
+      for (int b = 0; b < SUB; ++b) bf[b] = frag_read(Lb, wn * (TS / 2) + b * 16 + r16, u, g);
+      if (!FAST) __builtin_amdgcn_s_setprio(1);      // keeps the cluster contiguous (+1 % measured)
       mfma_step<SUB, 0, FAST>(acc, af, bf, keep);
       mfma_step<SUB, 1, FAST>(acc, af, bf, keep);
-      if (FAST && STORE_IN_SHADOW && u == 1) {
+      if (FAST && u == 1) {
         // the staging stores of the next panel are issued in the shadow of this half's MFMAs (one LDS write per few
         // MFMAs) instead of behind them: the prefetch landed thousands of cycles ago, and the pipe stays fed while the
         // wave issues them.  (B is staged even on a shared diagonal tile, where nobody reads it: no branch in the block.)
         double* Na = lds + (par ^ 1) * STAGE_LDS;
         panel_store<TS, AK>(Na, tid, ra);
         panel_store<TS, BKC>(Na + TILE_LDS, tid, rb);
-        if (LOADS_IN_SHADOW) {
-          // the whole iteration is one scheduling region; its order is pinned here.  First half: the fragment reads go out
-          // first, the next panel's global loads follow in the shadow of the first MFMAs (instead of standing between the
-          // barrier and the first MFMA), then the second half's fragment reads in the shadow of the rest.
-          __builtin_amdgcn_sched_group_barrier(0x100, 2 * SUB, 0);                     // DS read: fragments of half 0
+        // the whole iteration is one scheduling region; its order is pinned here.  First half: the fragment reads go out
+        // first, the next panel's global loads follow in the shadow of the first MFMAs (instead of standing between the
+        // barrier and the first MFMA), then the second half's fragment reads in the shadow of the rest.
+        __builtin_amdgcn_sched_group_barrier(0x100, 2 * SUB, 0);                     // DS read: fragments of half 0
 #pragma unroll
-          for (int i = 0; i < 2 * NQ; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, (SUB * SUB) / (2 * NQ), 0);     // MFMA
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                         // VMEM read
-          }
+        for (int i = 0; i < 2 * NQ; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, (SUB * SUB) / (2 * NQ), 0);     // MFMA
+          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                         // VMEM read
+        }
 #pragma unroll
-          for (int i = 0; i < 2 * SUB; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, (SUB * SUB) / (2 * SUB), 0);    // MFMA
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                         // DS read: fragments of half 1
-          }
+        for (int i = 0; i < 2 * SUB; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, (SUB * SUB) / (2 * SUB), 0);    // MFMA
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                         // DS read: fragments of half 1
         }
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
@@ -506,13 +471,11 @@ __global__ __launch_bounds__(NTHREADS, TS == 128 ? 2 : 4) void dgemm_tile_kernel
           __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                           // DS write
         }
       }
-      if (!(FAST && LOADS_IN_SHADOW) || u == 1) __builtin_amdgcn_s_setprio(0);
+      if (!FAST || u == 1) __builtin_amdgcn_s_setprio(0);
     }
-    if (more && !(FAST && STORE_IN_SHADOW)) {
-      if (!FAST) {
-        if (maskA && kn < i0 + BM && kn + BK > i0) panel_mask<TS, AK>(i0, kn, tid, keep_ge, p.tri_unit, ra);
-        if (maskB && kn < j0 + BN && kn + BK > j0) panel_mask<TS, BKC>(j0, kn, tid, keep_ge, p.tri_unit, rb);
-      }
+    if (more && !FAST) {
+      if (maskA && kn < i0 + BM && kn + BK > i0) panel_mask<TS, AK>(i0, kn, tid, keep_ge, p.tri_unit, ra);
+      if (maskB && kn < j0 + BN && kn + BK > j0) panel_mask<TS, BKC>(j0, kn, tid, keep_ge, p.tri_unit, rb);
       double* Na = lds + (par ^ 1) * STAGE_LDS;
       panel_store<TS, AK>(Na, tid, ra);
       if (!shareB) panel_store<TS, BKC>(Na + TILE_LDS, tid, rb);
@@ -628,8 +591,7 @@ __global__ __launch_bounds__(NTHREADS, TS == 128 ? 2 : 4) void dgemm_tile_kernel
 template <bool AK, bool BKC>
 __global__ __launch_bounds__(NTHREADS, 2) void dtrmm_pair_kernel(const GemmArgs p) {
   constexpr int TS = 128, BM = TS, BN = TS, SUB = tile_cfg<TS>::SUB, NQ = tile_cfg<TS>::NQ;
-  constexpr bool LOADS_IN_SHADOW = LOADS_IN_SHADOW_ON && ((AK && BKC) || TRANSPOSE_STAGE);
-  constexpr int NW = NQ * ((AK || !TRANSPOSE_STAGE ? 1 : 2) + (BKC || !TRANSPOSE_STAGE ? 1 : 2));
+  constexpr int NW = NQ * ((AK ? 1 : 2) + (BKC ? 1 : 2));
   constexpr int TILE_LDS = tile_cfg<TS>::TILE_LDS, STAGE_LDS = tile_cfg<TS>::STAGE_LDS;
   constexpr int kstep = BK;
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -650,10 +612,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void dtrmm_pair_kernel(const GemmArgs 
   const bool maskA = left, maskB = !left;
   const bool keep_ge = left == (p.tri_eff_upper != 0);
   const int64_t ksa = AK ? kstep : (int64_t)kstep * p.lda, ksb = BKC ? kstep : (int64_t)kstep * p.ldb;
-  const int64_t qsa = AK ? 32 * p.lda : TRANSPOSE_STAGE ? 8 * p.lda : (512 / TS) * p.lda;
-  const int64_t qsa2 = AK ? 64 * p.lda : TRANSPOSE_STAGE ? 16 : 2 * (512 / TS) * p.lda;
-  const int64_t qsb = BKC ? 32 * p.ldb : TRANSPOSE_STAGE ? 8 * p.ldb : (512 / TS) * p.ldb;
-  const int64_t qsb2 = BKC ? 64 * p.ldb : TRANSPOSE_STAGE ? 16 : 2 * (512 / TS) * p.ldb;
+  const int64_t qsa = AK ? 32 * p.lda : 8 * p.lda;
+  const int64_t qsa2 = AK ? 64 * p.lda : 16;
+  const int64_t qsb = BKC ? 32 * p.ldb : 8 * p.ldb;
+  const int64_t qsb2 = BKC ? 64 * p.ldb : 16;
 
   for (int ph = 0; ph < 2; ++ph) {
     const bool asc = (ph == 0) == anchor0;                 // phase 0 leaves the anchor, phase 1 returns to it
@@ -672,11 +634,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void dtrmm_pair_kernel(const GemmArgs 
 
     // per-thread source of panel 0 (see panel_load for the thread -> element map)
     const double* const fa0 = AK ? p.A + (int64_t)(i0 + (tid >> 3)) * p.lda + klo + 2 * (tid & 7)
-                              : TRANSPOSE_STAGE ? p.A + (int64_t)(klo + rc_k(tid, 0)) * p.lda + i0 + rc_r<TS>(tid, 0)
-                                                : p.A + (int64_t)(klo + tid / (TS / 2)) * p.lda + i0 + 2 * (tid & (TS / 2 - 1));
+                              : p.A + (int64_t)(klo + rc_k(tid, 0)) * p.lda + i0 + rc_r<TS>(tid, 0);
     const double* const fb0 = BKC ? p.B + (int64_t)(j0 + (tid >> 3)) * p.ldb + klo + 2 * (tid & 7)
-                              : TRANSPOSE_STAGE ? p.B + (int64_t)(klo + rc_k(tid, 0)) * p.ldb + j0 + rc_r<TS>(tid, 0)
-                                                : p.B + (int64_t)(klo + tid / (TS / 2)) * p.ldb + j0 + 2 * (tid & (TS / 2 - 1));
+                              : p.B + (int64_t)(klo + rc_k(tid, 0)) * p.ldb + j0 + rc_r<TS>(tid, 0);
     const double* fa = fa0;
     const double* fb = fb0;
     const int64_t sa = asc ? ksa : -ksa, sb = asc ? ksb : -ksb;
@@ -705,7 +665,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void dtrmm_pair_kernel(const GemmArgs 
       if (FAST) {
         fa += sa;
         fb += sb;
-        if (LOADS_IN_SHADOW) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
         panel_load_fast<TS>(fa, qsa, qsa2, ra);
         panel_load_fast<TS>(fb, qsb, qsb2, rb);
       } else if (more) {
@@ -736,28 +696,27 @@ __global__ __launch_bounds__(NTHREADS, 2) void dtrmm_pair_kernel(const GemmArgs 
       for (int u = 0; u < 2; ++u) {
         d2_t af[SUB], bf[SUB];
 #pragma unroll
-        for (int a = 0; a < SUB; ++a) af[a] = frag_read<TS, AK>(La, wm * (TS / 2) + a * 16 + r16, u, g);
+        for (int a = 0; a < SUB; ++a) af[a] = frag_read(La, wm * (TS / 2) + a * 16 + r16, u, g);
 #pragma unroll
-        for (int c = 0; c < SUB; ++c) bf[c] = frag_read<TS, BKC>(Lb, wn * (TS / 2) + c * 16 + r16, u, g);
-        if (!(FAST && LOADS_IN_SHADOW)) __builtin_amdgcn_s_setprio(1);
+        for (int c = 0; c < SUB; ++c) bf[c] = frag_read(Lb, wn * (TS / 2) + c * 16 + r16, u, g);
+        if (!FAST) __builtin_amdgcn_s_setprio(1);
         mfma_step<SUB, 0, FAST>(acc, af, bf, keep);
         mfma_step<SUB, 1, FAST>(acc, af, bf, keep);
-        if (FAST && STORE_IN_SHADOW && u == 1) {
+        if (FAST && u == 1) {
           double* Na = lds + (par ^ 1) * STAGE_LDS;
           panel_store<TS, AK>(Na, tid, ra);
           panel_store<TS, BKC>(Na + TILE_LDS, tid, rb);
-          if (LOADS_IN_SHADOW) {                                   // the pinned schedule of dgemm_tile_kernel's FAST iteration
-            __builtin_amdgcn_sched_group_barrier(0x100, 2 * SUB, 0);
+          // the pinned schedule of dgemm_tile_kernel's FAST iteration
+          __builtin_amdgcn_sched_group_barrier(0x100, 2 * SUB, 0);
 #pragma unroll
-            for (int i = 0; i < 2 * NQ; ++i) {
-              __builtin_amdgcn_sched_group_barrier(0x008, (SUB * SUB) / (2 * NQ), 0);
-              __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
+          for (int i = 0; i < 2 * NQ; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, (SUB * SUB) / (2 * NQ), 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+          }
 #pragma unroll
-            for (int i = 0; i < 2 * SUB; ++i) {
-              __builtin_amdgcn_sched_group_barrier(0x008, (SUB * SUB) / (2 * SUB), 0);
-              __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
+          for (int i = 0; i < 2 * SUB; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, (SUB * SUB) / (2 * SUB), 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
           }
 #pragma unroll
           for (int i = 0; i < NW; ++i) {
@@ -765,13 +724,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void dtrmm_pair_kernel(const GemmArgs 
             __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
           }
         }
-        if (!(FAST && LOADS_IN_SHADOW) || u == 1) __builtin_amdgcn_s_setprio(0);
+        if (!FAST || u == 1) __builtin_amdgcn_s_setprio(0);
       }
-      if (more && !(FAST && STORE_IN_SHADOW)) {
-        if (!FAST) {
-          if (maskA && tnext >= tb0 && tnext < tb1) panel_mask<TS, AK>(i0, kn, tid, keep_ge, p.tri_unit, ra);
-          if (maskB && tnext >= tb0 && tnext < tb1) panel_mask<TS, BKC>(j0, kn, tid, keep_ge, p.tri_unit, rb);
-        }
+      if (more && !FAST) {
+        if (maskA && tnext >= tb0 && tnext < tb1) panel_mask<TS, AK>(i0, kn, tid, keep_ge, p.tri_unit, ra);
+        if (maskB && tnext >= tb0 && tnext < tb1) panel_mask<TS, BKC>(j0, kn, tid, keep_ge, p.tri_unit, rb);
         double* Na = lds + (par ^ 1) * STAGE_LDS;
         panel_store<TS, AK>(Na, tid, ra);
         panel_store<TS, BKC>(Na + TILE_LDS, tid, rb);
@@ -1064,17 +1021,7 @@ gemm_kernel_t pick_small(bool ak, bool bkc) {
 // waves covers the FULL width, so every element of the tall operand travels global -> LDS exactly once.
 constexpr int TSK_THREADS = 512;
 using gemm_plan::TSK_W;                           // 256: 16 column strips of 16
-// the tall operands are read once and written once: non-temporal accesses (CAPI_TS_NT=0 compiles the plain ones, A/B)
-#ifndef CAPI_TS_NT
-#define CAPI_TS_NT 1
-#endif
-#if CAPI_TS_NT
-#define TS_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#define TS_LOAD(ptr) __builtin_nontemporal_load(ptr)
-#else
-#define TS_STORE(ptr, val) (*(ptr) = (val))
-#define TS_LOAD(ptr) (*(ptr))
-#endif
+// the tall operands are read once and written once: their accesses are non-temporal (__builtin_nontemporal_load / _store)
 
 // Gram matrix, upper triangle:  slab[z] (or C) = sum over this workgroup's k-range of A[k][i] A[k][j], A k-contiguous.
 // The 16 x 16 grid of output tiles has 136 upper tiles; wave w owns tile-rows w and 15-w (17 tiles): balanced, and per
@@ -1148,7 +1095,7 @@ __device__ __forceinline__ void gram_ts_body(const GemmArgs& p, double* __restri
     if (STEADY) {
       const double* src = p.A + (int64_t)c0 * acs + poff(pidx(it + 2)) + 2 * kp;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) nw[q] = TS_LOAD((const d2_t*)(src + (int64_t)(64 * q) * acs));
+      for (int q = 0; q < 4; ++q) nw[q] = __builtin_nontemporal_load((const d2_t*)(src + (int64_t)(64 * q) * acs));
     } else if (it + 2 < np) load(pidx(it + 2), nw);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -1321,7 +1268,7 @@ __device__ __forceinline__ void trmm_ts32_body(const GemmArgs& p, double* __rest
     if (STEADY) {
       const double* src = p.A + ats * (tile + dt) + lr + (int64_t)lc * acs;
 #pragma unroll
-      for (int q = 0; q < 8; ++q) st[q] = TS_LOAD((const d2_t*)(src + q * 32 * acs));
+      for (int q = 0; q < 8; ++q) st[q] = __builtin_nontemporal_load((const d2_t*)(src + q * 32 * acs));
     } else if (tile + dt < ntile) load(tile + dt, st);
     d4_t ca0 = {0.0, 0.0, 0.0, 0.0}, ca1 = ca0, cb0 = ca0, cb1 = ca0;
     const double* la = L + g * 16 + r16;                    // A[row 2 r16 (+1)][k = 4 s + g]
@@ -1359,8 +1306,8 @@ __device__ __forceinline__ void trmm_ts32_body(const GemmArgs& p, double* __rest
     if (STEADY) {
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
-        TS_STORE((d2_t*)(c0_ + reg * s4), ((d2_t){ca0[reg], ca1[reg]}));
-        TS_STORE((d2_t*)(c1_ + reg * s4), ((d2_t){cb0[reg], cb1[reg]}));
+        __builtin_nontemporal_store((d2_t){ca0[reg], ca1[reg]}, (d2_t*)(c0_ + reg * s4));
+        __builtin_nontemporal_store((d2_t){cb0[reg], cb1[reg]}, (d2_t*)(c1_ + reg * s4));
       }
     } else {
       const bool ok0 = i < p.M, ok1 = i + 1 < p.M;
