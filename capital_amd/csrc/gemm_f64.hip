@@ -1427,8 +1427,9 @@ int launch_reduce(capi_handle_t h, const GemmArgs& p, gemm_plan::Reduce kind) {
 }
 
 // Plans the product (gemm_plan.h) and launches what the plan says.  ws_for_slab: split-K partials go to the handle's primary
-// workspace; callers that already stage through it (in-place trmm) pass false.
-int launch_gemm(capi_handle_t h, bool ak, bool bkc, GemmArgs& p, bool ws_for_slab) {
+// workspace.  A caller that stages through that workspace itself (in-place trmm: C is its first ws_held doubles) says how much it
+// holds: the slabs go behind it, and when the block has to grow for them -- it moves -- p.C moves with it (nothing is in C yet).
+int launch_gemm(capi_handle_t h, bool ak, bool bkc, GemmArgs& p, bool ws_for_slab, size_t ws_held = 0) {
   using gemm_plan::Path;
   const GemmEnv& env = gemm_env();
   gemm_plan::Product d;
@@ -1519,9 +1520,11 @@ int launch_gemm(capi_handle_t h, bool ak, bool bkc, GemmArgs& p, bool ws_for_sla
   CAPI_REQUIRE(h, pl.blocks < (int64_t)1 << 31, "too many tiles");
   if (pl.splitk > 1) {
     void* ws;
-    int rc = capi_ws_get(h, sizeof(double) * (size_t)p.slab_stride * (size_t)p.splitk, &ws);
+    const uintptr_t was = (uintptr_t)h->ws[h->cur];
+    int rc = capi_ws_get(h, sizeof(double) * (ws_held + (size_t)p.slab_stride * (size_t)p.splitk), &ws);
     if (rc != CAPI_OK) return rc;
-    p.slab = (double*)ws;
+    if (ws_held && (uintptr_t)ws != was) p.C = (double*)((uintptr_t)ws + ((uintptr_t)p.C - was));
+    p.slab = (double*)ws + ws_held;
   }
   gemm_kernel_t k = p.ts == 128 ? pick_kernel<128>(ak, bkc) : pick_kernel<64>(ak, bkc);
   if (pl.path == Path::pair) {
@@ -1621,7 +1624,7 @@ int capi_dsyrk(capi_handle_t h, int uplo, int trans, int64_t n, int64_t k, doubl
 
 static int trmm_launch(capi_handle_t h, int side, int uplo, int trans, int diag, int64_t m, int64_t n, double alpha,
                        const double* T, int64_t ldt, const double* B, int64_t ldb, double beta, double* C, int64_t ldc,
-                       bool ws_free = true) {
+                       size_t ws_held = 0) {
   CAPI_REQUIRE(h, h, "null handle");
   CAPI_REQUIRE(h, ok01(side) && ok01(uplo) && ok01(trans) && ok01(diag), "enum code");
   CAPI_REQUIRE(h, m >= 0 && n >= 0 && m < (1LL << 31) && n < (1LL << 31), "dims");
@@ -1677,7 +1680,7 @@ static int trmm_launch(capi_handle_t h, int side, int uplo, int trans, int diag,
         // op(T)(k, j) for k < K, j in the block: NoTrans -> T[k + j ldt] (k-contiguous), Trans -> T[j + k ldt]
         q.B = trans == CAPI_NOTRANS ? T + 256 * J * ldt : T + 256 * J;
         q.ldb = ldt;
-        int rc2 = launch_gemm(h, false, trans == CAPI_NOTRANS, q, ws_free);
+        int rc2 = launch_gemm(h, false, trans == CAPI_NOTRANS, q, ws_held == 0);     // (every block's C would have to move: no split-K here)
         if (rc2 != CAPI_OK) return rc2;
       }
       return CAPI_OK;
@@ -1685,10 +1688,10 @@ static int trmm_launch(capi_handle_t h, int side, int uplo, int trans, int diag,
   }
   if (side == CAPI_LEFT) {  // C = alpha op(T) B : A-operand = T (transA = trans), B-operand = B (NoTrans)
     p.A = T; p.lda = ldt; p.B = B; p.ldb = ldb;
-    return launch_gemm(h, trans == CAPI_TRANS, true, p, ws_free);
+    return launch_gemm(h, trans == CAPI_TRANS, true, p, true, ws_held);
   } else {                  // C = alpha B op(T) : A-operand = B (NoTrans), B-operand = T (transB = trans)
     p.A = B; p.lda = ldb; p.B = T; p.ldb = ldt;
-    return launch_gemm(h, false, trans == CAPI_NOTRANS, p, ws_free);
+    return launch_gemm(h, false, trans == CAPI_NOTRANS, p, true, ws_held);
   }
 }
 
@@ -1737,7 +1740,10 @@ int capi_dtrmm(capi_handle_t h, int side, int uplo, int trans, int diag, int64_t
   void* ws;
   int rc = capi_ws_get(h, sizeof(double) * (size_t)m * (size_t)n, &ws);
   if (rc != CAPI_OK) return rc;
-  rc = trmm_launch(h, side, uplo, trans, diag, m, n, alpha, T, ldt, B, ldb, 0.0, (double*)ws, m, /*ws_free=*/false);
+  // (the product is planned like the out-of-place one -- thin shapes are split along k -- and so has its bits)
+  rc = trmm_launch(h, side, uplo, trans, diag, m, n, alpha, T, ldt, B, ldb, 0.0, (double*)ws, m, /*ws_held=*/(size_t)m * (size_t)n);
+  if (rc != CAPI_OK) return rc;
+  rc = capi_ws_get(h, sizeof(double) * (size_t)m * (size_t)n, &ws);          // the block may have grown, and moved, for the slabs
   if (rc != CAPI_OK) return rc;
   return capi_internal_copy2d(h, m, n, (const double*)ws, m, B, ldb);
 }

@@ -83,6 +83,108 @@ def test_potrf_reports_non_spd(hip, oracle):
     assert hip.info() == 0
 
 
+@pytest.mark.parametrize("fn,uplo,n,j,j2", [("capi_dpotrf_trtri", 1, 300, 200, 230),      # second leaf of the blocked routine (j2: same leaf)
+                                            ("capi_dpotrf", 1, 1500, 1100, 1400),          # second order-1024 block, inner leaf
+                                            ("capi_dpotrf", 0, 1500, 1100, 1400),          # ... through the transpose
+                                            ("capi_dpotrf_trtri", 1, 4200, 3000, 3500)])   # the halving recursion: info_base + n1
+def test_info_index_beyond_the_first_leaf(hip, oracle, fn, uplo, n, j, j2):
+    """A[j, j] = -5 in an SPD matrix: the first leading minor that is not positive definite has order j + 1, which is LAPACK's info
+    whatever the blocking -- every leaf, block and recursion level must add its own offset.  A second bad pivot further down must lose."""
+    from capital_amd import capi
+    A = _spd(oracle, n)
+    A[j, j] = -5.0
+    A[j2, j2] = -5.0
+    hip.call("capi_reset_info")
+    assert hip.info() == 0
+    dA = capi.to_device(A)
+    if fn == "capi_dpotrf_trtri":
+        dX = capi.zeros(n, n)
+        hip.call(fn, n, capi.ptr(dA), n, capi.ptr(dX), n)
+    else:
+        hip.call(fn, uplo, n, capi.ptr(dA), n)
+    assert hip.info() == j + 1
+    if n <= 1500:
+        assert oracle.dpotrf(uplo, A.copy(order="F")) == j + 1
+    hip.call("capi_reset_info")
+    assert hip.info() == 0
+
+
+def _padded(A, ld, fill):
+    """A on top of ld - n rows of `fill`: the device image is column-major with leading dimension ld."""
+    n = A.shape[0]
+    out = np.full((ld, A.shape[1]), fill, order="F")
+    out[:n] = A
+    return out
+
+
+_bits = lambda a: np.ascontiguousarray(a).view(np.int64)
+
+
+# cholinv.h calls the factor routines on sub-blocks (ld > n): test_potrf_trtri_fused, test_potrf and test_trtri once more with lda = n + 3
+# and ldi = n + 5 -- same references and tolerances, and the rows between n and ld stay as they were, bit for bit
+@pytest.mark.parametrize("n", [513, 1600])
+def test_potrf_trtri_fused_padded_ld(hip, oracle, n):
+    from capital_amd import capi
+    lda, ldi = n + 3, n + 5
+    A = _spd(oracle, n)
+    Rref = A.copy(order="F")
+    assert oracle.dpotrf(1, Rref) == 0
+    Rref = np.triu(Rref)
+    Xref = Rref.copy(order="F")
+    assert oracle.dtrtri(1, 0, Xref) == 0
+    Ap, Xp = _padded(A, lda, 7.25), _padded(np.full((n, n), np.nan), ldi, -3.5)
+    dA, dX = capi.to_device(Ap), capi.to_device(Xp)
+    hip.call("capi_reset_info")
+    hip.call("capi_dpotrf_trtri", n, capi.ptr(dA), lda, capi.ptr(dX), ldi)
+    assert hip.info() == 0
+    R, X = capi.to_host(dA), capi.to_host(dX)
+    assert np.abs(R[:n] - Rref).max() <= 1e-12 * np.abs(Rref).max()
+    assert np.abs(X[:n] - np.triu(Xref)).max() <= 1e-12 * np.abs(Xref).max()
+    assert np.all(np.tril(R[:n], -1) == 0) and np.all(np.tril(X[:n], -1) == 0)
+    assert np.array_equal(_bits(R[n:]), _bits(Ap[n:])) and np.array_equal(_bits(X[n:]), _bits(Xp[n:]))
+
+
+@pytest.mark.parametrize("uplo", (0, 1))
+@pytest.mark.parametrize("n", [513, 1600])
+def test_potrf_padded_ld(hip, oracle, uplo, n):
+    from capital_amd import capi
+    lda = n + 3
+    A = _spd(oracle, n)
+    ref = A.copy(order="F")
+    assert oracle.dpotrf(uplo, ref) == 0
+    Ap = _padded(A, lda, 7.25)
+    dA = capi.to_device(Ap)
+    hip.call("capi_reset_info")
+    hip.call("capi_dpotrf", uplo, n, capi.ptr(dA), lda)
+    assert hip.info() == 0
+    got = capi.to_host(dA)
+    tri = np.triu(np.ones((n, n), bool)) if uplo else np.tril(np.ones((n, n), bool))
+    assert np.abs(got[:n][tri] - ref[tri]).max() <= 1e-12 * np.abs(ref[tri]).max()
+    assert np.array_equal(_bits(got[:n][~tri]), _bits(A[~tri]))     # LAPACK leaves the other triangle alone
+    assert np.array_equal(_bits(got[n:]), _bits(Ap[n:]))
+
+
+@pytest.mark.parametrize("uplo,diag", [(1, 0), (0, 1)])
+@pytest.mark.parametrize("n", [513, 1600])
+def test_trtri_padded_ld(hip, oracle, uplo, diag, n):
+    from capital_amd import capi
+    lda = n + 3
+    rng = np.random.default_rng(n + uplo + diag)
+    T = np.asfortranarray(rng.uniform(-1, 1, (n, n)) * 0.1 + np.eye(n) * 3)
+    ref = T.copy(order="F")
+    assert oracle.dtrtri(uplo, diag, ref) == 0
+    Tp = _padded(T, lda, 7.25)
+    dT = capi.to_device(Tp)
+    hip.call("capi_dtrtri", uplo, diag, n, capi.ptr(dT), lda)
+    hip.sync()
+    got = capi.to_host(dT)
+    tri = np.triu(np.ones((n, n), bool), 1 if diag else 0) if uplo else np.tril(np.ones((n, n), bool), -1 if diag else 0)
+    assert np.abs(got[:n][tri] - ref[tri]).max() <= 1e-12 * max(1.0, np.abs(ref[tri]).max())
+    other = ~(np.triu(np.ones((n, n), bool)) if uplo else np.tril(np.ones((n, n), bool)))
+    assert np.array_equal(_bits(got[:n][other]), _bits(T[other]))
+    assert np.array_equal(_bits(got[n:]), _bits(Tp[n:]))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("m,n", [(64, 64), (100, 37), (300, 96), (1000, 130), (33, 70)])
 def test_geqrf_matches_oracle(hip, oracle, m, n):

@@ -94,6 +94,56 @@ def test_lacpy_trizero_axpby_remove_triangle(hip, oracle):
         np.testing.assert_array_equal(capi.to_host(dL), ref)
 
 
+def _fma_exact(alpha, X, beta, Y):
+    """fl(beta * y + fl(alpha * x)), the sum and the product beta * y rounded ONCE: exact rational arithmetic, correctly rounded."""
+    from fractions import Fraction
+    ax, out, fb = alpha * X, np.empty_like(X), Fraction(beta)
+    for idx in np.ndindex(X.shape):
+        out[idx] = float(fb * Fraction(float(Y[idx])) + Fraction(float(ax[idx])))
+    return out
+
+
+@pytest.mark.parametrize("part,m,n", [(p, m, n) for m, n in ((150, 140), (1, 1), (513, 9), (1024, 1024)) for p in (0, 1, 2) if p or m < 1024])
+def test_geadd(hip, part, m, n):
+    """capi_dgeadd, Y(part) = alpha X + beta Y: the beta-axpy of every SUMMA product (parts 1 / 2: the triangular-output forms) and the
+    final accumulation of cholinv::solve; triangle convention of capi_dlacpy.  The kernel does one multiply and one multiply-add per
+    element, and the compiler contracts the latter (v_fmac_f64: beta * y is not rounded on its own).  So: the result equals
+    fl(beta y + fl(alpha x)) BIT FOR BIT (checked in exact arithmetic at the small shapes, signed operands), and numpy's twice-rounded
+    alpha * X + beta * Y to 1 ulp of the result (operands of one sign: the two forms differ by half an ulp of beta y, which nothing
+    bounds by the result when the terms cancel).  Everything outside the part, and the padding rows, stays as it was."""
+    import torch
+    from capital_amd import capi
+    rng = np.random.default_rng(100 * m + 10 * n + part)
+    ldx, ldy = m + 2, m + 5
+    X, Y = rng.uniform(-1, 1, size=(ldx, n)), rng.uniform(-1, 1, size=(ldy, n))
+    i, j = np.indices((m, n))
+    sel = np.ones((m, n), bool) if part == 0 else (i <= j if part == 1 else i >= j)
+    bits = lambda a: np.ascontiguousarray(a).view(np.int64)
+
+    def run(alpha, Xh, beta, Yh, x_is_y=False):
+        dY = capi.to_device(Yh)
+        dX = dY if x_is_y else capi.to_device(Xh)
+        torch.cuda.synchronize()
+        hip.call("capi_dgeadd", part, m, n, alpha, capi.ptr(dX), ldy if x_is_y else ldx, beta, capi.ptr(dY), ldy)
+        hip.sync()
+        got = capi.to_host(dY)
+        assert np.array_equal(bits(got[:m][~sel]), bits(Yh[:m][~sel])), "outside the part"
+        assert np.array_equal(bits(got[m:]), bits(Yh[m:])), "padding rows"
+        return got[:m][sel]
+
+    if m * n <= 25000:
+        got = run(-1.5, X, -0.75, Y)
+        assert np.array_equal(bits(got), bits(_fma_exact(-1.5, X[:m][sel], -0.75, Y[:m][sel])))
+    Xp, Yp = np.abs(X), np.abs(Y)
+    got, ref = run(0.75, Xp, 1.25, Yp), (0.75 * Xp[:m] + 1.25 * Yp[:m])[sel]
+    assert np.all(np.abs(got - ref) <= np.spacing(ref))
+    Ynan = np.full((ldy, n), np.nan)
+    got = run(0.0, None, 0.0, Ynan, x_is_y=True)                      # the Y = 0 idiom of summa.h: alpha = beta = 0, X == Y
+    assert np.array_equal(bits(got), bits(np.zeros(got.shape)))
+    got = run(1.0, X, 0.0, Ynan)                                      # beta == 0 never reads Y
+    assert np.array_equal(bits(got), bits(X[:m][sel]))
+
+
 @pytest.mark.parametrize("rl,d", [(8, 2), (5, 3), (16, 1)])
 def test_block_cyclic(hip, oracle, rl, d):
     import ctypes as C
