@@ -1,0 +1,368 @@
+// sym_apply_f64.hip -- a SYMMETRIC matrix, given by its upper triangle, times a thin block (r <= 32 columns): the residual of the solves on the
+// cholinv factors (cholesky::cholinv::solve).  Not in the reference: its cholinv stops at R and R^-1.
+//
+//   capi_dresid_sym   Rout (n x r) <- B - S X, colnorm2[j] <- sum_i Rout(i, j)^2      S = triu(A) + triu(A, 1)^T, column-major A
+//
+// The upper triangle is read from HBM once; nothing below A's diagonal is read into a result.  The triangle is cut into a p x p block triangle,
+// one workgroup per block (sym_thin_plan.h).  A 32 x 32 tile U of block (I, J) feeds two products: U X_J goes to the lines of I and U^T X_I to
+// the lines of J, both on v_mfma_f64_16x16x4_f64 with the r columns padded to 16.  This kernel serves r < 8 (SY_TWO_PASS_FROM below): from there on
+// two capi_dtrmm_thin passes over the same triangle and a correction of the diagonal measured faster, and the call runs those.
+// The two products want the tile in two operand layouts (the contraction index sits on lane >> 4: columns for U X, rows for U^T X).  The tile is
+// LOADED TWICE, in the load shapes of trmm_thin_kernel's NOTRANS and TRANS forms, one behind the other: the second load finds the lines of the first
+// in flight or in L2, not in HBM.  An LDS transpose and lane permutes are not built.
+// A workgroup of 8 waves walks its block in super-tiles of 256 x 256, column of super-tiles by column.  Inside one, wave w owns the row strip
+// 32 w.. and takes the column strips (w + t) mod 8, t = 0..7:
+//   U X_J    accumulates in registers over the 8 steps, then into the block's row slot (read-modify-write by the one wave that owns the strip)
+//   U^T X_I  goes to an LDS image of the 256 columns after every step: the 8 waves are on 8 different strips, a barrier separates the steps, so
+//            a strip receives its terms in a fixed order; the image goes to the block's column slot when the column of super-tiles is done
+// X_J (256 x 16) stays in LDS for a column of super-tiles, X_I is double-buffered per super-tile; A's pieces are double-buffered in registers, one
+// step ahead (one loop body: the prefetched set is moved, not a second copy of the body with the sets swapped -- that copy spilt 300 VGPRs).
+// A second launch adds the p + 1 slots of every line block in a fixed order, subtracts from B and forms the squared norms per 256
+// lines, a third adds those in order: no floating-point atomics, the same bits on every run.
+// Edges (ragged blocks, the tiles the diagonal crosses): every element from a clamped address, selected afterwards (never multiplied by zero):
+// the diagonal tile gives row <= col to U X and row < col to U^T X.  Columns are loaded 16 bytes at a time from 8-byte-aligned addresses, as
+// tri_apply_f64.hip does.
+#include "capi_internal.h"
+#include "sym_thin_plan.h"
+
+namespace {
+
+namespace sp = sym_thin_plan;
+
+typedef double d4_t __attribute__((ext_vector_type(4)));
+typedef double d2_t __attribute__((ext_vector_type(2)));
+typedef d2_t d2u_t __attribute__((aligned(8)));      // a row pair of a column that is 8-byte aligned only
+
+constexpr int SY_THREADS = 512;                 // 8 waves, one workgroup per CU
+constexpr int SY_NP = 8;                        // 16-byte pieces of a tile per lane and operand form
+constexpr int SY_IMG = sp::SUPER * sp::RPAD;    // doubles of one LDS image: 256 lines x 16 columns
+constexpr size_t SY_LDS = sizeof(double) * 4 * SY_IMG;   // X_J, X_I twice, the column sums: 128 KiB
+
+struct SymArgs {
+  const double* A; const double* X; double* slab;
+  int64_t lda, ldx;
+  int r;
+  sp::Plan P;
+};
+
+__global__ __launch_bounds__(SY_THREADS) void resid_sym_kernel(const SymArgs p) {
+  extern __shared__ __attribute__((aligned(16))) double Ls[];   // [4][256][16]: X_J(k, j), X_I(k, j) twice, (U^T X_I)(col, j)
+  double* const XJ = Ls;
+  double* const XI = Ls + SY_IMG;
+  double* const P2 = Ls + 3 * SY_IMG;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l16 = lane & 15, g4 = lane >> 4;
+  int I, J;
+  sp::block_of((int)blockIdx.x, &I, &J);
+  const bool diag = I == J;
+  const int64_t n = p.P.n, bs = p.P.bs;
+  const int64_t r0 = sp::line0(p.P, I), r1 = sp::line1(p.P, I), c0 = sp::line0(p.P, J), c1 = sp::line1(p.P, J);
+  const int nsr = (int)sp::cdiv64(r1 - r0, sp::SUPER), nsc = (int)sp::cdiv64(c1 - c0, sp::SUPER);
+  const int total = 8 * (diag ? nsc * (nsc + 1) / 2 : nsr * nsc);            // steps: 8 per super-tile
+  double* const slab1 = p.slab + (int64_t)sp::slot_of(I, J, 0) * sp::slot_doubles(p.P);
+  double* const slab2 = p.slab + (int64_t)sp::slot_of(I, J, 1) * sp::slot_doubles(p.P);
+  auto last_row = [&](int C) { return diag ? C : nsr - 1; };                 // the last super-tile of column C
+
+  // ---- the thin operand: thread t fetches line t & 255 of columns (t >> 8) + 2 q ----
+  const int fk = tid & (sp::SUPER - 1), fj = tid >> 8;
+  double xst[8];
+  auto xload = [&](int64_t k0) {
+    const int64_t k = k0 + fk;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int j = fj + 2 * q;
+      const bool in = k < n && j < p.r;
+      xst[q] = *(in ? p.X + k + (int64_t)j * p.ldx : p.X);
+    }
+  };
+  auto xstore = [&](double* L, int64_t k0) {
+    const int64_t k = k0 + fk;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int j = fj + 2 * q;
+      L[fk * 16 + j] = (k < n && j < p.r) ? xst[q] : 0.0;
+    }
+  };
+
+  // ---- the tile of wave w at step t of super-tile (R, C): rows row0.., columns col0.. ----
+  auto origin = [&](int C, int R, int t, int64_t* row0, int64_t* col0) {
+    *row0 = r0 + (int64_t)R * sp::SUPER + 32 * w;
+    *col0 = c0 + (int64_t)C * sp::SUPER + 32 * ((w + t) & 7);
+  };
+  // wave-uniform: the tile holds something / is whole and strictly above the diagonal
+  auto live = [&](int C, int R, int t) {
+    int64_t row0, col0;
+    origin(C, R, t, &row0, &col0);
+    return row0 < r1 && col0 < c1 && (!diag || row0 <= col0);
+  };
+  auto steady = [&](int C, int R, int t) {
+    int64_t row0, col0;
+    origin(C, R, t, &row0, &col0);
+    return row0 + 32 <= r1 && col0 + 32 <= c1 && (!diag || row0 < col0);
+  };
+  // form N: rows row0 + 2 l16, + 1 of column col0 + 4 q + g4.   form T: rows row0 + 8 (q & 3) + 2 g4, + 1 of column col0 + 16 (q >> 2) + l16
+  // (a lane's place inside the tile is a 32-bit offset from the tile's first element, which is wave-uniform: one address register per lane)
+  const uint32_t ld32 = (uint32_t)p.lda;
+  const uint32_t offn = (uint32_t)g4 * ld32 + 2 * (uint32_t)l16, offt = (uint32_t)l16 * ld32 + 2 * (uint32_t)g4;
+  auto load_steady = [&](int C, int R, int t, d2_t (&na)[SY_NP], d2_t (&ta)[SY_NP]) {
+    int64_t row0, col0;
+    origin(C, R, t, &row0, &col0);
+    const double* tb = p.A + col0 * p.lda + row0;
+#pragma unroll
+    for (int q = 0; q < SY_NP; ++q) na[q] = *(const d2u_t*)(tb + (int64_t)(4 * q) * p.lda + offn);
+#pragma unroll
+    for (int q = 0; q < SY_NP; ++q) ta[q] = __builtin_nontemporal_load((const d2u_t*)(tb + (int64_t)(16 * (q >> 2)) * p.lda + 8 * (q & 3) + offt));
+  };
+  auto load_edge = [&](int C, int R, int t, d2_t (&na)[SY_NP], d2_t (&ta)[SY_NP]) {
+    int64_t row0, col0;
+    origin(C, R, t, &row0, &col0);
+    const double* tb = p.A + col0 * p.lda + row0;                        // the tile's first element: inside the block, on or above the diagonal
+    const int rows = (int)sp::min64(32, r1 - row0), cols = (int)sp::min64(32, c1 - col0);
+    const int dg = diag ? (int)(col0 - row0) : 64;                       // row <= col  <=>  i <= j + dg in the tile's own indices
+#pragma unroll
+    for (int q = 0; q < SY_NP; ++q) {
+      const int i = 2 * l16, j = 4 * q + g4;
+      const bool v0 = i < rows && j < cols && i <= j + dg, v1 = i + 1 < rows && j < cols && i + 1 <= j + dg;       // U X: the diagonal takes part
+      const uint32_t o = (uint32_t)j * ld32 + (uint32_t)i;
+      const double x = tb[v0 ? o : 0u], y = tb[v1 ? o + 1u : 0u];
+      na[q] = (d2_t){v0 ? x : 0.0, v1 ? y : 0.0};
+    }
+#pragma unroll
+    for (int q = 0; q < SY_NP; ++q) {
+      const int i = 8 * (q & 3) + 2 * g4, j = 16 * (q >> 2) + l16;
+      const bool v0 = i < rows && j < cols && i < j + dg, v1 = i + 1 < rows && j < cols && i + 1 < j + dg;         // U^T X: it does not
+      const uint32_t o = (uint32_t)j * ld32 + (uint32_t)i;
+      const double x = tb[v0 ? o : 0u], y = tb[v1 ? o + 1u : 0u];
+      ta[q] = (d2_t){v0 ? x : 0.0, v1 ? y : 0.0};
+    }
+  };
+
+  d4_t acc1[2];
+  int par = 0;
+  // one step: prefetch the following step's pieces (a whole tile's), multiply this one's
+  auto step = [&](int C, int R, int t, d2_t (&na)[SY_NP], d2_t (&ta)[SY_NP], d2_t (&nna)[SY_NP], d2_t (&nta)[SY_NP], int nC, int nR, int nt,
+                  bool has_next) {
+    // an edge tile is fetched where it is used, not a step ahead: its selects beside a second set of pieces cost spills, and the blocks
+    // that hold edge tiles (the diagonal's, the ragged last ones) are the short ones
+    if (live(C, R, t) && !steady(C, R, t)) load_edge(C, R, t, na, ta);
+    if (has_next && live(nC, nR, nt) && steady(nC, nR, nt)) load_steady(nC, nR, nt, nna, nta);
+    const bool tile_end = t == 7, col_end = tile_end && R == last_row(C);     // workgroup-uniform
+    if (t == 0) { acc1[0] = (d4_t){0.0, 0.0, 0.0, 0.0}; acc1[1] = (d4_t){0.0, 0.0, 0.0, 0.0}; }
+    if (tile_end && !col_end) xload(r0 + (int64_t)(R + 1) * sp::SUPER);
+    const int c = (w + t) & 7;
+    if (live(C, R, t)) {
+      d4_t acc2[2] = {(d4_t){0.0, 0.0, 0.0, 0.0}, (d4_t){0.0, 0.0, 0.0, 0.0}};
+      const double* xj = XJ + (32 * c + g4) * 16 + l16;
+      const double* xi = XI + par * SY_IMG + (32 * w + 2 * g4) * 16 + l16;
+      __builtin_amdgcn_s_setprio(1);
+      // acc1[h]: lane (l16, g4) holds (U X_J)(row0 + 2 l16 + h, g4 + 4 reg)
+#pragma unroll
+      for (int q = 0; q < SY_NP; ++q) {
+        const double xv = xj[4 * q * 16];
+        acc1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, na[q].x, acc1[0], 0, 0, 0);
+        acc1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, na[q].y, acc1[1], 0, 0, 0);
+      }
+      // acc2[s]: lane (l16, g4) holds (U^T X_I)(col0 + 16 s + g4 + 4 reg, l16)
+#pragma unroll
+      for (int q = 0; q < SY_NP; ++q) {
+        const double b0 = xi[8 * (q & 3) * 16], b1 = xi[(8 * (q & 3) + 1) * 16];
+        acc2[q >> 2] = __builtin_amdgcn_mfma_f64_16x16x4f64(ta[q].x, b0, acc2[q >> 2], 0, 0, 0);
+        acc2[q >> 2] = __builtin_amdgcn_mfma_f64_16x16x4f64(ta[q].y, b1, acc2[q >> 2], 0, 0, 0);
+      }
+      __builtin_amdgcn_s_setprio(0);
+      double* pc = P2 + (32 * c + g4) * 16 + l16;
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) pc[(16 * s + 4 * reg) * 16] += acc2[s][reg];
+    }
+    if (tile_end && r0 + (int64_t)R * sp::SUPER + 32 * w < r1) {
+      // the strip's sums over this super-tile join those of the columns before it: only this wave touches these lines of the row slot
+      const bool first = C == (diag ? R : 0);
+      double* sl = slab1 + (int64_t)R * sp::SUPER + 32 * w + 2 * l16;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        d2_t v = {acc1[0][reg], acc1[1][reg]};
+        d2_t* dst = (d2_t*)(sl + (int64_t)(g4 + 4 * reg) * bs);
+        if (!first) v += *dst;
+        *dst = v;
+      }
+    }
+    if (tile_end && !col_end) xstore(XI + (par ^ 1) * SY_IMG, r0 + (int64_t)(R + 1) * sp::SUPER);
+    __syncthreads();
+    if (tile_end && !col_end) par ^= 1;
+    if (col_end) {
+      // the column sums of this column of super-tiles: to the column slot, and zero again
+      for (int e = tid; e < SY_IMG; e += SY_THREADS) {
+        const int i = e & (sp::SUPER - 1), j = e >> 8;
+        const int64_t x = (int64_t)C * sp::SUPER + i;
+        if (x < bs) slab2[(int64_t)j * bs + x] = P2[i * 16 + j];
+        P2[i * 16 + j] = 0.0;
+      }
+      if (has_next) {
+        xload(c0 + (int64_t)(C + 1) * sp::SUPER);
+        xstore(XJ, c0 + (int64_t)(C + 1) * sp::SUPER);
+        xload(r0);
+        xstore(XI + par * SY_IMG, r0);
+      }
+      __syncthreads();
+    }
+  };
+
+  for (int e = tid; e < SY_IMG; e += SY_THREADS) P2[e] = 0.0;
+  xload(c0);
+  xstore(XJ, c0);
+  xload(r0);
+  xstore(XI, r0);
+  d2_t na[SY_NP], ta[SY_NP], nna[SY_NP], nta[SY_NP];
+  if (live(0, 0, 0) && steady(0, 0, 0)) load_steady(0, 0, 0, na, ta);
+  __syncthreads();
+  int C = 0, R = 0, t = 0;
+  for (int q = 0; q < total; ++q) {
+    int nC = C, nR = R, nt = t + 1;
+    if (nt == 8) { nt = 0; if (++nR > last_row(C)) { nR = 0; ++nC; } }
+    step(C, R, t, na, ta, nna, nta, nC, nR, nt, q + 1 < total);
+#pragma unroll
+    for (int i = 0; i < SY_NP; ++i) { na[i] = nna[i]; ta[i] = nta[i]; }
+    C = nC; R = nR; t = nt;
+  }
+}
+
+struct SymCombineArgs {
+  const double* slab; const double* B; double* R; double* part;
+  int64_t ldb, ldr;
+  int r;
+  sp::Plan P;
+};
+
+// Rout(l, j) = B(l, j) - (the p + 1 slots of l's line block, in the plan's order); part[group][j] = the squared norms over the group's 256 lines
+__global__ __launch_bounds__(sp::SUPER) void resid_sym_combine_kernel(const SymCombineArgs p) {
+  __shared__ double red[sp::RPAD][4];
+  const int tid = threadIdx.x;
+  const int64_t l = (int64_t)blockIdx.x * sp::SUPER + tid;
+  const bool in = l < p.P.n;
+  const int L = in ? (int)(l / p.P.bs) : 0;
+  const int64_t x = in ? l - (int64_t)L * p.P.bs : 0, sd = sp::slot_doubles(p.P);
+  for (int j = 0; j < p.r; ++j) {
+    double sq = 0.0;
+    if (in) {
+      double sum = 0.0;
+      for (int k = 0; k <= p.P.p; ++k) sum += p.slab[(int64_t)sp::contribution(p.P, L, k) * sd + (int64_t)j * p.P.bs + x];
+      const double v = p.B[l + (int64_t)j * p.ldb] - sum;
+      if (p.R) p.R[l + (int64_t)j * p.ldr] = v;
+      sq = v * v;
+    }
+    // a fixed butterfly inside the wave, then the four waves in order
+    sq += __shfl_xor(sq, 1);
+    sq += __shfl_xor(sq, 2);
+    sq += __shfl_xor(sq, 4);
+    sq += __shfl_xor(sq, 8);
+    sq += __shfl_xor(sq, 16);
+    sq += __shfl_xor(sq, 32);
+    if ((tid & 63) == 0) red[j][tid >> 6] = sq;
+  }
+  __syncthreads();
+  if (p.part && tid < p.r) p.part[(int64_t)blockIdx.x * sp::RPAD + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
+}
+
+// the two-pass route's last step: W = U X + U^T X counted the diagonal twice.  Rout(l, j) = B(l, j) - (W(l, j) - A(l, l) X(l, j)); part as above,
+// CAPI_TS_MAX_RHS columns per group
+__global__ __launch_bounds__(sp::SUPER) void resid_sym_finish_kernel(const double* __restrict__ W, const double* __restrict__ A, int64_t lda,
+                                                                     const double* __restrict__ X, int64_t ldx, const double* B, int64_t ldb, double* R,
+                                                                     int64_t ldr, double* __restrict__ part, int64_t n, int r) {
+  __shared__ double red[CAPI_TS_MAX_RHS][4];
+  const int tid = threadIdx.x;
+  const int64_t l = (int64_t)blockIdx.x * sp::SUPER + tid;
+  const bool in = l < n;
+  const double d = in ? A[l + l * lda] : 0.0;
+  for (int j = 0; j < r; ++j) {
+    double sq = 0.0;
+    if (in) {
+      const double v = B[l + (int64_t)j * ldb] - (W[l + (int64_t)j * n] - d * X[l + (int64_t)j * ldx]);
+      if (R) R[l + (int64_t)j * ldr] = v;
+      sq = v * v;
+    }
+    sq += __shfl_xor(sq, 1);
+    sq += __shfl_xor(sq, 2);
+    sq += __shfl_xor(sq, 4);
+    sq += __shfl_xor(sq, 8);
+    sq += __shfl_xor(sq, 16);
+    sq += __shfl_xor(sq, 32);
+    if ((tid & 63) == 0) red[j][tid >> 6] = sq;
+  }
+  __syncthreads();
+  if (part && tid < r) part[(int64_t)blockIdx.x * CAPI_TS_MAX_RHS + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
+}
+
+// colnorm2[j] = part[group 0][j] + part[group 1][j] + ..  (groups of `stride` doubles)
+__global__ __launch_bounds__(64) void resid_sym_norms_kernel(const double* __restrict__ part, int64_t groups, int stride, int r, double* __restrict__ colnorm2) {
+  const int j = threadIdx.x;
+  if (j >= r) return;
+  double sum = 0.0;
+  for (int64_t g = 0; g < groups; ++g) sum += part[g * stride + j];
+  colnorm2[j] = sum;
+}
+
+// From this many columns on the call takes the two-pass route: capi_dtrmm_thin NOTRANS and TRANS over the same triangle (read twice), then the
+// diagonal's correction.  Measured (profiles/resid_sym.txt): the fused kernel ties with it at r = 1 and loses at r = 8 (4 % at n = 32768, 8 % at
+// 16384) and at r = 32 (1.4 x: it needs two passes of 16 columns itself); between 1 and 8 nothing is measured.
+constexpr int SY_TWO_PASS_FROM = 8;
+
+}  // namespace
+
+extern "C" {
+
+int capi_dresid_sym(capi_handle_t h, int64_t n, int64_t r, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B, int64_t ldb,
+                    double* Rout, int64_t ldr, double* colnorm2) {
+  CAPI_REQUIRE(h, h, "null handle");
+  CAPI_REQUIRE(h, r >= 1 && r <= CAPI_TS_MAX_RHS, "r: 1 <= r <= CAPI_TS_MAX_RHS (32) right-hand sides per call");
+  CAPI_REQUIRE(h, n >= 0 && n < (1LL << 31) && lda < (1LL << 24), "n / lda (lda < 2^24: 32 columns are addressed by 32-bit byte offsets)");
+  CAPI_REQUIRE(h, n == 0 || (A && X && B && lda >= n && ldx >= n && ldb >= n && (!Rout || ldr >= n)), "A/lda/X/ldx/B/ldb/Rout/ldr");
+  CAPI_REQUIRE(h, !Rout || Rout != X, "Rout must not alias X");
+  if (n == 0) {
+    if (colnorm2) hipLaunchKernelGGL(resid_sym_norms_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)nullptr, (int64_t)0, sp::RPAD, (int)r, colnorm2);
+    CAPI_HIP_CHECK(h, hipGetLastError());
+    return CAPI_OK;
+  }
+  const int64_t groups = cdiv(n, sp::SUPER);
+  if (r >= SY_TWO_PASS_FROM) {
+    // W (n x r) and the norms' partial sums lie in the second workspace block: capi_dtrmm_thin keeps its slabs in the first
+    void* pw = nullptr;
+    int rc = capi_ws2_get(h, sizeof(double) * (size_t)(n * r + groups * CAPI_TS_MAX_RHS), &pw);
+    if (rc != CAPI_OK) return rc;
+    double* W = (double*)pw;
+    double* part = W + n * r;
+    rc = capi_dtrmm_thin(h, CAPI_UPPERTRI, CAPI_NOTRANS, n, n, r, 1.0, A, lda, 0, X, ldx, 0.0, W, n);
+    if (rc != CAPI_OK) return rc;
+    rc = capi_dtrmm_thin(h, CAPI_UPPERTRI, CAPI_TRANS, n, n, r, 1.0, A, lda, 0, X, ldx, 1.0, W, n);
+    if (rc != CAPI_OK) return rc;
+    hipLaunchKernelGGL(resid_sym_finish_kernel, dim3((unsigned)groups), dim3(sp::SUPER), 0, h->stream, (const double*)W, A, lda, X, ldx, B, ldb, Rout, ldr,
+                       colnorm2 ? part : (double*)nullptr, n, (int)r);
+    if (colnorm2) hipLaunchKernelGGL(resid_sym_norms_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)part, groups, (int)CAPI_TS_MAX_RHS, (int)r, colnorm2);
+    CAPI_HIP_CHECK(h, hipGetLastError());
+    return CAPI_OK;
+  }
+  const int cus = h->cu_of[h->cur] > 0 ? h->cu_of[h->cur] : h->num_cu;
+  const sp::Plan P = sp::make_plan(n, cus);
+  void* pv = nullptr;
+  int rc = capi_ws_get(h, sizeof(double) * (size_t)(sp::slab_doubles(P) + groups * sp::RPAD), &pv);
+  if (rc != CAPI_OK) return rc;
+  double* slab = (double*)pv;
+  double* part = slab + sp::slab_doubles(P);
+  CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_RESID_SYM, resid_sym_kernel, SY_LDS);
+  SymArgs p;
+  p.A = A; p.X = X; p.slab = slab;
+  p.lda = lda; p.ldx = ldx;
+  p.r = (int)r; p.P = P;
+  hipLaunchKernelGGL(resid_sym_kernel, dim3((unsigned)sp::num_blocks(P)), dim3(SY_THREADS), SY_LDS, h->stream, p);
+  SymCombineArgs cp;
+  cp.slab = slab; cp.B = B; cp.R = Rout; cp.part = colnorm2 ? part : nullptr;
+  cp.ldb = ldb; cp.ldr = ldr;
+  cp.r = (int)r; cp.P = P;
+  hipLaunchKernelGGL(resid_sym_combine_kernel, dim3((unsigned)groups), dim3(sp::SUPER), 0, h->stream, cp);
+  if (colnorm2) hipLaunchKernelGGL(resid_sym_norms_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)part, groups, sp::RPAD, (int)r, colnorm2);
+  CAPI_HIP_CHECK(h, hipGetLastError());
+  return CAPI_OK;
+}
+
+}  // extern "C"

@@ -172,7 +172,8 @@ class Cholinv:
         """A X = B on the factors of the last factor() (cholesky::cholinv::solve, one rank): products with the resident R^-1 -- block-wise with
         R^-1_11, R^-1_22 and R_12 where complete_inv=0 skipped R^-1_12 -- or capi_dtrsm on R in TRSM mode, then `refine` steps of
         fixed-precision refinement.  B: n x r.  Returns (X, resnorms): X n x r; resnorms[j] = ||b_j - A x_j||_2, or None with residual=False.
-        refine > 0 and residual read both triangles of A: A must be stored symmetric (generate(), or set_A of a symmetric array)."""
+        Like factor(), the refinement and the residual norms read A's upper triangle alone (capi_dresid_sym): what set_A left below the diagonal is
+        never used."""
         b = np.asfortranarray(B, dtype=np.float64)
         if b.ndim == 1:
             b = np.asfortranarray(b[:, None])

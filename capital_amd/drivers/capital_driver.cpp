@@ -236,7 +236,8 @@ int capital_cholinv_dims(void* p, int64_t* nloc, int* x, int* y, int* z, int* d,
 int capital_cholinv_stats(void* p, int64_t* bc, int64_t* levels, int64_t* bcdim) { return guarded([&] { ((cholinv_problem*)p)->stats(bc, levels, bcdim); }); }
 // TRSM mode (info::solve_with_trsm): potrf + block TRSM + SYRK recursion, no inverse formed (one GPU, or a d x d x c grid: potrf_rec_grid)
 int capital_cholinv_set_trsm_mode(void* p, int on) { return guarded([&] { ((cholinv_problem*)p)->set_trsm_mode(on != 0); }); }
-// A X = B on the factors (cholesky::cholinv::solve): after capital_cholinv_factor, one rank; resnorm_host_or_null == NULL skips the residual pass
+// A X = B on the factors (cholesky::cholinv::solve): after capital_cholinv_factor, one rank; resnorm_host_or_null == NULL skips the residual pass.
+// Refinement and residual read A's upper triangle alone, as the factorization does: A need not be stored symmetric
 int capital_cholinv_solve(void* p, int64_t r, const double* B_host, double* X_host, double* resnorm_host_or_null, int refine) {
   return guarded([&] { ((cholinv_problem*)p)->solve(r, B_host, X_host, resnorm_host_or_null, refine); });
 }

@@ -20,9 +20,11 @@
 #include "./policy.h"
 
 // The thin triangular product of solve() is a weak reference, as cacqr.h has its four: a stand-in of the C-ABI without it (the CPU rehearsal
-// shims of the test suite) still links and loads, factor() runs on it as before, and solve() refuses.
+// shims of the test suite) still links and loads, factor() runs on it as before, and solve() refuses.  capi_dresid_sym is weak on its own: a
+// library that has the other two but not it still solves, with capi_dresid_ts over all of A (which must then be stored symmetric).
 #pragma weak capi_dtrmm_thin
 #pragma weak capi_dresid_ts
+#pragma weak capi_dresid_sym
 
 namespace cholesky {
 
@@ -222,10 +224,11 @@ public:
   //   complete_inv == 0 and the top level split at h1 (R^-1_12 was never formed):
   //       y1 = R11^-T b1,  y2 = R22^-T (b2 - R12^T y1),  x2 = R22^-1 y2,  x1 = R11^-1 (y1 - R12 x2)      -- the same bytes as the complete form
   //   TRSM mode (no inverse exists): X = R^-1 R^-T B by capi_dtrsm on a full-storage R (Rfull where resident, or the rect structure)
-  // `refine` steps of fixed-precision refinement follow (rho = B - A X by capi_dresid_ts, X += solve(rho)): multiplying by an explicit inverse
+  // `refine` steps of fixed-precision refinement follow (rho = B - A X by capi_dresid_sym, X += solve(rho)): multiplying by an explicit inverse
   // is not backward stable in general, one step restores a backward error at the level of u for kappa u < 1.  The refinement and the residual
-  // norms read BOTH triangles of A, where factor() reads the upper one only: with refine > 0 or residual, A must be stored symmetric
-  // (distribute_symmetric, or from_host of a symmetric array).  refine == 0 and residual == false do not touch A.
+  // norms read A's UPPER triangle alone, as factor() does (capi_dresid_sym: a tile of the triangle serves the lines of its rows and, transposed,
+  // of its columns): what lies below the diagonal is never used, in any mode.  (With a C-ABI library that lacks capi_dresid_sym both passes fall back to
+  // capi_dresid_ts over all of A, which reads both triangles.)  refine == 0 and residual == false do not touch A.
   template <typename MatrixType, typename ArgType, typename CommType>
   static void solve(const MatrixType& A, const MatrixType& B, ArgType& args, CommType&& CommInfo, int refine = 1, bool residual = true) {
     static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::solve takes rect-structured A and B");
@@ -287,13 +290,18 @@ public:
         thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, 0, 0, h1, h1, rb, 1.0, w1, 0.0, Xo);                       // x1 = R11^-1 (..)
       }
     };
+    // Ro (or nothing) <- Bi - A Xi, norm2 (or nothing) <- its squared column norms, from A's upper triangle
+    auto resid = [&](int64_t rb, const double* Xi, const double* Bi, double* Ro, double* norm2) {
+      if (&capi_dresid_sym) { CAPITAL_CHECK(capi_dresid_sym(h, n, rb, A.data(), n, Xi, n, Bi, n, Ro, Ro ? n : 0, norm2)); }
+      else { CAPITAL_CHECK(capi_dresid_ts(h, n, n, rb, A.data(), n, Xi, n, Bi, n, Ro, Ro ? n : 0, norm2)); }
+    };
     for (int64_t j = 0; j < r; j += W) {
       const int64_t rb = std::min(W, r - j);
       double* Xj = args.X.data() + j * n;
       const double* Bj = B.data() + j * n;
       apply(Bj, Xj, rb);
       for (int it = 0; it < refine; ++it) {
-        CAPITAL_CHECK(capi_dresid_ts(h, n, n, rb, A.data(), n, Xj, n, Bj, n, args.SolveRho.data(), n, nullptr));
+        resid(rb, Xj, Bj, args.SolveRho.data(), nullptr);
         apply(args.SolveRho.data(), args.SolveD.data(), rb);
         CAPITAL_CHECK(capi_dgeadd(h, 0, n, rb, 1.0, args.SolveD.data(), n, 1.0, Xj, n));
       }
@@ -302,9 +310,7 @@ public:
     if (residual) {
       if (args.SolveNorm2.filled() && args.SolveNorm2.num_columns_local() != r) args.SolveNorm2._destroy_();
       args.SolveNorm2._register_(r, 1, 1, 1);
-      for (int64_t j = 0; j < r; j += W)
-        CAPITAL_CHECK(capi_dresid_ts(h, n, n, std::min(W, r - j), A.data(), n, args.X.data() + j * n, n, B.data() + j * n, n, nullptr, 0,
-                                     args.SolveNorm2.data() + j));
+      for (int64_t j = 0; j < r; j += W) resid(std::min(W, r - j), args.X.data() + j * n, B.data() + j * n, nullptr, args.SolveNorm2.data() + j);
       args.solve_residual_norms = args.SolveNorm2.to_host();
       for (double& v : args.solve_residual_norms) v = std::sqrt(v);
     }

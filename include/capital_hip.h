@@ -163,6 +163,19 @@ int capi_dresid_ts(capi_handle_t h, int64_t m, int64_t n, int64_t r, const doubl
  * the entries below the diagonal take part as zeros (0 * B(k)), so a NaN or Inf in B reaches output lines that it does not belong to. */
 int capi_dtrmm_thin(capi_handle_t h, int shape, int trans, int64_t m, int64_t n, int64_t r, double alpha,
                     const double* T, int64_t ldt, int64_t col0, const double* B, int64_t ldb, double beta, double* C, int64_t ldc);
+/* capi_dresid_sym: Rout (n x r) <- B - S X and colnorm2[j] <- sum_i Rout(i, j)^2 (DEVICE, r doubles) for the SYMMETRIC S whose upper triangle, diagonal
+ * included, is that of the column-major A (lda >= n): the residual of cholesky::cholinv::solve.  Not in the reference: cholinv.hpp stops at R and R^-1.
+ * NO element below A's diagonal influences any output: it may hold NaN, Inf or garbage (inside the tiles that the diagonal crosses the unwanted
+ * elements are removed by a select, not multiplied by zero).  Below 8 columns the upper triangle is read from HBM ONCE, by a kernel of its own: a
+ * tile serves S X's lines of its rows and, transposed, of its columns.  From 8 columns on the call runs capi_dtrmm_thin(CAPI_UPPERTRI) twice,
+ * NOTRANS and TRANS, and corrects the diagonal, which both counted: the triangle is read twice, and that measured faster there.
+ * Every other convention is capi_dresid_ts's: Rout == NULL: the norms alone; Rout == B: in place; colnorm2 == NULL: the residual alone; n == 0:
+ * colnorm2 <- 0; 1 <= r <= CAPI_TS_MAX_RHS (more: CAPI_EINVAL, nothing is touched); pointers aligned to 8 bytes, any leading dimensions (lda < 2^24).
+ * Rout must not alias X.  Partial sums are combined in a fixed order: bit-identical from run to run, no atomics.
+ * Workspace, of the handle's own.  Below 8 columns: p (p + 1) blocks of 16 x bs doubles, p (p + 1) / 2 <= the CUs and bs = n / p rounded up to 32 --
+ * about 128 p n bytes, 93 MiB at n = 32768 on 256 CUs (p = 22), 2 % of the triangle.  From 8 on: capi_dtrmm_thin's, and n x r doubles. */
+int capi_dresid_sym(capi_handle_t h, int64_t n, int64_t r, const double* A, int64_t lda, const double* X, int64_t ldx,
+                    const double* B, int64_t ldb, double* Rout, int64_t ldr, double* colnorm2);
 /* LAPACKE_dgeqrf / LAPACKE_dorgqr behind lapack::engine::_geqrf / _orgqr (lapack/interface.hpp:60-88; the reference has
  * the slots but no caller -- CholeskyQR2 is its QR).  Householder QR, LAPACK storage: R in the upper triangle, the
  * reflectors v_j (unit first entry implied) below it, tau[min(m,n)] on the DEVICE.  capi_dorgqr overwrites A (m x n,

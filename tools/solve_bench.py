@@ -6,11 +6,19 @@ the same process:
   (b) the device copy of tools/hbm_copy_bench.py (b.copy_(a)) sized to MOVE the triangle's bytes (a copy of N bytes moves 2 N)
   (c) the route through the earlier entry points: capi_serialize to full storage where the operand is packed, plus capi_dtrmm_oop on r columns
 
-for n = 16384 and 32768 and r = 1, 8, 32: warm-up, then `--reps` alternating rounds, median and min..max.  With --e2e N one Cholinv.solve
+for n = 16384 and 32768 and r = 1, 8, 32: warm-up, then `--reps` alternating rounds, median and min..max.  With --resid ORDERS the residual
+pass of solve, Rout <- B - S X with its norms on a symmetric S, by three routes and the copy, alternating in the same way:
+
+  (a) capi_dresid_sym on the upper triangle
+  (b) capi_dresid_ts over all of A (what solve ran before capi_dresid_sym existed)
+  (c) two capi_dtrmm_thin(CAPI_UPPERTRI) calls on full storage, NOTRANS and TRANS, and a diagonal correction (two elementwise device kernels;
+      no norms): the triangle read twice, with no kernel of its own
+
+With --e2e N one Cholinv.solve
 (config 2's policies: complete_inv = 0, split = 1, Serialize) beside its factor().  The parent process makes no GPU call: every order runs in a
 child of its own under a time limit, and a failed child ends the run.
 
-    python tools/solve_bench.py [--reps 9] [--orders 16384,32768] [--e2e 32768] [--limit 300]"""
+    python tools/solve_bench.py [--reps 9] [--orders 16384,32768] [--resid 16384,32768] [--e2e 32768] [--limit 300]"""
 import argparse
 import os
 import statistics
@@ -105,6 +113,72 @@ def child(n, reps, warmup):
     h.close()
 
 
+def resid_child(n, reps, warmup):
+    import ctypes as C
+    import torch
+    from capital_amd import capi
+    h = capi.Handle(0)
+    dev = "cuda:0"
+    g = torch.Generator(device=dev).manual_seed(2)
+    p = capi.ptr
+    # a symmetric n x n matrix in full storage (row j of the tensor is column j of the matrix: the same thing)
+    A = torch.empty((n, n), dtype=torch.float64, device=dev)
+    for j0 in range(0, n, 4096):
+        A[j0:j0 + 4096] = torch.randn((min(4096, n - j0), n), dtype=torch.float64, device=dev, generator=g) * (1.0 / n ** 0.5)
+    A = torch.triu(A)
+    A += torch.triu(A, 1).T
+    diag = torch.diagonal(A).clone()
+    np_ = n * (n + 1) // 2
+    h.sync()
+    ms = C.c_float()
+
+    def timed(fn):
+        h.call("capi_timer_start")
+        fn()
+        h.call("capi_timer_stop_ms", C.byref(ms))
+        return ms.value
+
+    print(f"== residual pass, n = {n}: the upper triangle is {8 * np_ / 1e9:.2f} GB, all of A {8 * n * n / 1e9:.2f} GB; {reps} alternating rounds after "
+          f"{warmup} warm-up rounds; capi version {h.L.capi_version()}", flush=True)
+    for r in (1, 8, 32):
+        X = torch.randn((r, n), dtype=torch.float64, device=dev, generator=g)
+        B = torch.randn((r, n), dtype=torch.float64, device=dev, generator=g)
+        Ra, Rb, Rc = capi.zeros(n, r), capi.zeros(n, r), capi.zeros(n, r)
+        na, nb = torch.zeros(r, dtype=torch.float64, device=dev), torch.zeros(r, dtype=torch.float64, device=dev)
+        csrc = torch.empty(np_ // 2, dtype=torch.float64, device=dev).normal_()
+        cdst = torch.empty_like(csrc)
+
+        def route_c():
+            h.call("capi_dtrmm_thin", capi.UPPERTRI, capi.NOTRANS, n, n, r, -1.0, p(A), n, 0, p(X), n, 0.0, p(Rc), n)
+            h.call("capi_dtrmm_thin", capi.UPPERTRI, capi.TRANS, n, n, r, -1.0, p(A), n, 0, p(X), n, 1.0, p(Rc), n)
+            Rc.add_(B).addcmul_(X, diag)                                  # both products counted the diagonal
+
+        steps = {
+            "a.dresid_sym": lambda: h.call("capi_dresid_sym", n, r, p(A), n, p(X), n, p(B), n, p(Ra), n, p(na)),
+            "b.dresid_ts.full": lambda: h.call("capi_dresid_ts", n, n, r, p(A), n, p(X), n, p(B), n, p(Rb), n, p(nb)),
+            "c.thin_N+T.full": route_c,
+            "copy": lambda: cdst.copy_(csrc),
+        }
+        times = {k: [] for k in steps}
+        for i in range(warmup + reps):
+            for k, fn in steps.items():
+                tm = timed(fn)
+                if i >= warmup:
+                    times[k].append(tm)
+        h.sync()
+        scale = max(Rb.abs().max().item(), 1e-300)
+        print(f"-- r = {r}:  max |R_a - R_b| / max |R_b| = {(Ra - Rb).abs().max().item() / scale:.2e}, max |R_c - R_b| / max |R_b| = "
+              f"{(Rc - Rb).abs().max().item() / scale:.2e}, max |norm_a - norm_b| / norm_b = {((na - nb).abs() / nb).max().item():.2e}")
+        med = {k: statistics.median(v) for k, v in times.items()}
+        for k in steps:
+            ts = times[k]
+            print(f"   {k:20s} {statistics.median(ts):8.3f} ms [{min(ts):.3f} .. {max(ts):.3f}]   spread {(max(ts) - min(ts)) / med[k] * 100:4.1f} %"
+                  f"   (b) / this = {med['b.dresid_ts.full'] / med[k]:.2f}")
+        print(f"   the copy moves {8 * np_ / 1e9:.2f} GB: {8 * np_ / med['copy'] / 1e9:.2f} TB/s at its median", flush=True)
+        del X, B, Ra, Rb, Rc, csrc, cdst
+    h.close()
+
+
 def e2e(n):
     import numpy as np
     from capital_amd import driver
@@ -142,6 +216,7 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--orders", default="16384,32768")
+    ap.add_argument("--resid", default="", help="orders of the residual pass: capi_dresid_sym against capi_dresid_ts and two capi_dtrmm_thin calls")
     ap.add_argument("--e2e", type=int, default=0, help="order of one end-to-end factor() + solve (0: none)")
     ap.add_argument("--limit", type=int, default=300, help="seconds per child")
     ap.add_argument("--child", default=None)
@@ -149,10 +224,12 @@ def main():
     if a.child:
         if a.child.startswith("e2e:"):
             e2e(int(a.child[4:]))
+        elif a.child.startswith("resid:"):
+            resid_child(int(a.child[6:]), a.reps, a.warmup)
         else:
             child(int(a.child), a.reps, a.warmup)
         return 0
-    jobs = [o for o in a.orders.split(",") if o] + ([f"e2e:{a.e2e}"] if a.e2e else [])
+    jobs = [o for o in a.orders.split(",") if o] + [f"resid:{o}" for o in a.resid.split(",") if o] + ([f"e2e:{a.e2e}"] if a.e2e else [])
     for job in jobs:
         try:
             rc = subprocess.run([sys.executable, "-u", os.path.abspath(__file__), "--child", job, "--reps", str(a.reps), "--warmup", str(a.warmup)],
