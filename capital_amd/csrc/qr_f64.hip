@@ -300,6 +300,8 @@ int block_reflector(capi_handle_t h, const double* Apanel, int64_t lda, int64_t 
 // (T = -U S Y1^-T), and the rows below the top block are Y2 = Q2 U^-1: one more tall product.
 // Used only when CholeskyQR2 is safe: both Gram matrices factor (device info) and the first sweep's R has a diagonal ratio below 1e6
 // (kappa(A) well inside the u^-1/2 limit); otherwise A is untouched and the Householder panels above run.  n <= 2048.
+// Where a column is already reduced when its turn comes, dlarfg returns H = I (tau = 0) and the LU above the other valid reflector,
+// I - 2 e_j e_j^T (tau = 2, row j of R negated): hr_identity_reflector_kernel rewrites those columns into dlarfg's form.
 constexpr int HRNB = 32;
 
 // unblocked LU without pivoting of an (rows x nb) panel whose pivot block starts at P; sgn[c] = the sign subtracted from pivot c
@@ -331,6 +333,23 @@ __global__ void hr_assemble_kernel(double* __restrict__ A, int64_t lda, const do
   if (i >= n) return;
   for (int j = blockIdx.y; j < n; j += gridDim.y) A[i + (int64_t)j * lda] = i > j ? W[i + (int64_t)j * n] : sgn[i] * R[i + (int64_t)j * n];
   if (blockIdx.y == 0) tau[i] = -sgn[i] * W[i + (int64_t)i * n];
+}
+
+// A column that is already a multiple of e_j when its turn comes (x = 0) has TWO valid reflectors: dlarfg's H_j = I (tau = 0, row j
+// of R untouched) and the reconstruction's H_j = I - 2 e_j e_j^T (tau = 1 + |q_jj| = 2, v_j = e_j, row j of R negated).  This puts such
+// columns into dlarfg's form.  One workgroup per column; a column whose tau is not 2 to within 2^-40 leaves after reading that one value
+// (a reflector with a nonzero entry has tau = 2 / ||v||^2 < 2, and 1 + |q_jj| reaches 2 only where the rest of q_j has rounded away),
+// so the panel is read again only in the columns that may need it.  Workgroup j reads A(j+1:m, j) and writes A(j, j:n) and tau[j]:
+// no other workgroup reads or writes those.
+__global__ void hr_identity_reflector_kernel(double* __restrict__ A, int64_t lda, int64_t m, int n, double* __restrict__ tau) {
+  const int j = blockIdx.x;
+  if (!(tau[j] >= 2.0 - 0x1p-40)) return;
+  const double* x = A + (int64_t)j * lda;
+  int nz = 0;
+  for (int64_t r = (int64_t)j + 1 + threadIdx.x; r < m; r += blockDim.x) nz |= x[r] != 0.0;
+  if (__syncthreads_or(nz)) return;
+  for (int c = j + (int)threadIdx.x; c < n; c += (int)blockDim.x) A[j + (int64_t)c * lda] = -A[j + (int64_t)c * lda];
+  if (threadIdx.x == 0) tau[j] = 0.0;
 }
 
 __global__ void hr_diag_ratio_kernel(const double* __restrict__ R, int n, double* __restrict__ out2) {   // one workgroup: min and max |r_ii|
@@ -403,6 +422,7 @@ int geqrf_tall_reconstruct(capi_handle_t h, int64_t m, int64_t n, double* A, int
   HR(capi_dtrtri(h, CAPI_UPPER, CAPI_NONUNIT, n, Ui, n));
   if (m > n) HR(capi_dtrmm_oop(h, CAPI_RIGHT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, m - n, n, 1.0, Ui, n, Q2 + n, m, A + n, lda));
   hipLaunchKernelGGL(hr_assemble_kernel, dim3((unsigned)cdiv(n, 256), (unsigned)(n < 65535 ? n : 65535)), dim3(256), 0, s, A, lda, W, Rf, sgn, (int)n, tau);
+  hipLaunchKernelGGL(hr_identity_reflector_kernel, dim3((unsigned)n), dim3(256), 0, s, A, lda, m, (int)n, tau);   // tau = 2, v = e_j -> tau = 0 (dlarfg)
   if (hipGetLastError() != hipSuccess) return fail(CAPI_EHIP);
 #undef HR
   *done = 1;

@@ -179,7 +179,9 @@ int capi_dresid_sym(capi_handle_t h, int64_t n, int64_t r, const double* A, int6
 /* LAPACKE_dgeqrf / LAPACKE_dorgqr behind lapack::engine::_geqrf / _orgqr (lapack/interface.hpp:60-88; the reference has
  * the slots but no caller -- CholeskyQR2 is its QR).  Householder QR, LAPACK storage: R in the upper triangle, the
  * reflectors v_j (unit first entry implied) below it, tau[min(m,n)] on the DEVICE.  capi_dorgqr overwrites A (m x n,
- * m >= n >= k) with the first n columns of Q = H_1 ... H_k.  Blocked (compact WY, width 32) on the MFMA tile kernel. */
+ * m >= n >= k) with the first n columns of Q = H_1 ... H_k.  Blocked (compact WY, width 32) on the MFMA tile kernel.
+ * Tall panels (32 <= n <= 2048, m >= 64 n) are factored by CholeskyQR2 and the LAPACK image reconstructed from it; the output is
+ * dlarfg's on either side of that gate, tau = 0 for a column that is already reduced included.  k == 0: tau may be NULL. */
 int capi_dgeqrf(capi_handle_t h, int64_t m, int64_t n, double* A, int64_t lda, double* tau);
 int capi_dorgqr(capi_handle_t h, int64_t m, int64_t n, int64_t k, double* A, int64_t lda, const double* tau);
 int capi_reset_info(capi_handle_t h);
