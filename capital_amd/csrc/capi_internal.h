@@ -101,5 +101,12 @@ int capi_ws4_get(capi_handle_t h, size_t bytes, void** p);
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// the entry points of the thin kernels (ts_apply_f64.hip, tri_apply_f64.hip, sym_apply_f64.hip): r <= CAPI_TS_MAX_RHS columns per call, padded to
+// rb = 1 or 2 planes of 16 columns (rpad = 16 rb)
+#define CAPI_REQUIRE_THIN_R(h, r) CAPI_REQUIRE(h, (r) >= 1 && (r) <= CAPI_TS_MAX_RHS, "r: 1 <= r <= CAPI_TS_MAX_RHS (32) columns per call")
+static inline int capi_thin_rb(int64_t r) { return r > 16 ? 2 : 1; }
+// CUs the selected stream may use: its CU mask's, or all
+static inline int capi_stream_cus(capi_handle_t h) { return h->cu_of[h->cur] > 0 ? h->cu_of[h->cur] : h->num_cu; }
+
 // hipFree, or (CAPI_DEFER_FREE) remember the block until capi_destroy
 hipError_t capi_release(capi_handle_t h, void* p);

@@ -7,9 +7,9 @@
 // one workgroup per block (sym_thin_plan.h).  A 32 x 32 tile U of block (I, J) feeds two products: U X_J goes to the lines of I and U^T X_I to
 // the lines of J, both on v_mfma_f64_16x16x4_f64 with the r columns padded to 16.  This kernel serves r < 8 (SY_TWO_PASS_FROM below): from there on
 // two capi_dtrmm_thin passes over the same triangle and a correction of the diagonal measured faster, and the call runs those.
-// The two products want the tile in two operand layouts (the contraction index sits on lane >> 4: columns for U X, rows for U^T X).  The tile is
-// LOADED TWICE, in the load shapes of trmm_thin_kernel's NOTRANS and TRANS forms, one behind the other: the second load finds the lines of the first
-// in flight or in L2, not in HBM.  An LDS transpose and lane permutes are not built.
+// The two products want the tile in the two operand forms of thin_tile.h (row dots for U X, column dots for U^T X).  The tile is LOADED TWICE, once
+// in each form, one behind the other: the second load finds the lines of the first in flight or in L2, not in HBM.  An LDS transpose and lane
+// permutes are not built.
 // A workgroup of 8 waves walks its block in super-tiles of 256 x 256, column of super-tiles by column.  Inside one, wave w owns the row strip
 // 32 w.. and takes the column strips (w + t) mod 8, t = 0..7:
 //   U X_J    accumulates in registers over the 8 steps, then into the block's row slot (read-modify-write by the one wave that owns the strip)
@@ -20,18 +20,18 @@
 // A second launch adds the p + 1 slots of every line block in a fixed order, subtracts from B and forms the squared norms per 256
 // lines, a third adds those in order: no floating-point atomics, the same bits on every run.
 // Edges (ragged blocks, the tiles the diagonal crosses): every element from a clamped address, selected afterwards (never multiplied by zero):
-// the diagonal tile gives row <= col to U X and row < col to U^T X.  Columns are loaded 16 bytes at a time from 8-byte-aligned addresses, as
-// tri_apply_f64.hip does.
+// the diagonal tile gives row <= col to U X and row < col to U^T X.  Columns are loaded 16 bytes at a time from 8-byte-aligned addresses (d2u_t).
 #include "capi_internal.h"
 #include "sym_thin_plan.h"
+#include "thin_tile.h"
 
 namespace {
 
 namespace sp = sym_thin_plan;
-
-typedef double d4_t __attribute__((ext_vector_type(4)));
-typedef double d2_t __attribute__((ext_vector_type(2)));
-typedef d2_t d2u_t __attribute__((aligned(8)));      // a row pair of a column that is 8-byte aligned only
+namespace tt = thin_tile;
+using tt::d2_t;
+using tt::d2u_t;
+using tt::d4_t;
 
 constexpr int SY_THREADS = 512;                 // 8 waves, one workgroup per CU
 constexpr int SY_NP = 8;                        // 16-byte pieces of a tile per lane and operand form
@@ -100,8 +100,8 @@ __global__ __launch_bounds__(SY_THREADS) void resid_sym_kernel(const SymArgs p) 
     origin(C, R, t, &row0, &col0);
     return row0 + 32 <= r1 && col0 + 32 <= c1 && (!diag || row0 < col0);
   };
-  // form N: rows row0 + 2 l16, + 1 of column col0 + 4 q + g4.   form T: rows row0 + 8 (q & 3) + 2 g4, + 1 of column col0 + 16 (q >> 2) + l16
-  // (a lane's place inside the tile is a 32-bit offset from the tile's first element, which is wave-uniform: one address register per lane)
+  // form N (na): the row-dot pieces; form T (ta): the column-dot pieces.  A lane's place inside the tile is a 32-bit offset from the tile's first
+  // element, which is wave-uniform: one address register per lane
   const uint32_t ld32 = (uint32_t)p.lda;
   const uint32_t offn = (uint32_t)g4 * ld32 + 2 * (uint32_t)l16, offt = (uint32_t)l16 * ld32 + 2 * (uint32_t)g4;
   auto load_steady = [&](int C, int R, int t, d2_t (&na)[SY_NP], d2_t (&ta)[SY_NP]) {
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(SY_THREADS) void resid_sym_kernel(const SymArgs p) 
     }
   };
 
-  d4_t acc1[2];
+  d4_t acc1[2][1];                       // (U X_J)(row0 + 2 l16 + h, g4 + 4 reg)
   int par = 0;
   // one step: prefetch the following step's pieces (a whole tile's), multiply this one's
   auto step = [&](int C, int R, int t, d2_t (&na)[SY_NP], d2_t (&ta)[SY_NP], d2_t (&nna)[SY_NP], d2_t (&nta)[SY_NP], int nC, int nR, int nt,
@@ -147,34 +147,20 @@ __global__ __launch_bounds__(SY_THREADS) void resid_sym_kernel(const SymArgs p) 
     if (live(C, R, t) && !steady(C, R, t)) load_edge(C, R, t, na, ta);
     if (has_next && live(nC, nR, nt) && steady(nC, nR, nt)) load_steady(nC, nR, nt, nna, nta);
     const bool tile_end = t == 7, col_end = tile_end && R == last_row(C);     // workgroup-uniform
-    if (t == 0) { acc1[0] = (d4_t){0.0, 0.0, 0.0, 0.0}; acc1[1] = (d4_t){0.0, 0.0, 0.0, 0.0}; }
+    if (t == 0) { acc1[0][0] = (d4_t){0.0, 0.0, 0.0, 0.0}; acc1[1][0] = (d4_t){0.0, 0.0, 0.0, 0.0}; }
     if (tile_end && !col_end) xload(r0 + (int64_t)(R + 1) * sp::SUPER);
     const int c = (w + t) & 7;
     if (live(C, R, t)) {
-      d4_t acc2[2] = {(d4_t){0.0, 0.0, 0.0, 0.0}, (d4_t){0.0, 0.0, 0.0, 0.0}};
-      const double* xj = XJ + (32 * c + g4) * 16 + l16;
-      const double* xi = XI + par * SY_IMG + (32 * w + 2 * g4) * 16 + l16;
+      d4_t acc2[2][1] = {{(d4_t){0.0, 0.0, 0.0, 0.0}}, {(d4_t){0.0, 0.0, 0.0, 0.0}}};   // (U^T X_I)(col0 + 16 s + g4 + 4 reg, l16)
       __builtin_amdgcn_s_setprio(1);
-      // acc1[h]: lane (l16, g4) holds (U X_J)(row0 + 2 l16 + h, g4 + 4 reg)
-#pragma unroll
-      for (int q = 0; q < SY_NP; ++q) {
-        const double xv = xj[4 * q * 16];
-        acc1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, na[q].x, acc1[0], 0, 0, 0);
-        acc1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, na[q].y, acc1[1], 0, 0, 0);
-      }
-      // acc2[s]: lane (l16, g4) holds (U^T X_I)(col0 + 16 s + g4 + 4 reg, l16)
-#pragma unroll
-      for (int q = 0; q < SY_NP; ++q) {
-        const double b0 = xi[8 * (q & 3) * 16], b1 = xi[(8 * (q & 3) + 1) * 16];
-        acc2[q >> 2] = __builtin_amdgcn_mfma_f64_16x16x4f64(ta[q].x, b0, acc2[q >> 2], 0, 0, 0);
-        acc2[q >> 2] = __builtin_amdgcn_mfma_f64_16x16x4f64(ta[q].y, b1, acc2[q >> 2], 0, 0, 0);
-      }
+      tt::mfma_row_dots<1>(acc1, XJ + (32 * c + g4) * 16 + l16, 0, na);
+      tt::mfma_col_dots<1>(acc2, XI + par * SY_IMG + (32 * w + 2 * g4) * 16 + l16, 0, ta);
       __builtin_amdgcn_s_setprio(0);
       double* pc = P2 + (32 * c + g4) * 16 + l16;
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) pc[(16 * s + 4 * reg) * 16] += acc2[s][reg];
+        for (int reg = 0; reg < 4; ++reg) pc[(16 * s + 4 * reg) * 16] += acc2[s][0][reg];
     }
     if (tile_end && r0 + (int64_t)R * sp::SUPER + 32 * w < r1) {
       // the strip's sums over this super-tile join those of the columns before it: only this wave touches these lines of the row slot
@@ -182,7 +168,7 @@ __global__ __launch_bounds__(SY_THREADS) void resid_sym_kernel(const SymArgs p) 
       double* sl = slab1 + (int64_t)R * sp::SUPER + 32 * w + 2 * l16;
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
-        d2_t v = {acc1[0][reg], acc1[1][reg]};
+        d2_t v = {acc1[0][0][reg], acc1[1][0][reg]};
         d2_t* dst = (d2_t*)(sl + (int64_t)(g4 + 4 * reg) * bs);
         if (!first) v += *dst;
         *dst = v;
@@ -237,32 +223,18 @@ struct SymCombineArgs {
 
 // Rout(l, j) = B(l, j) - (the p + 1 slots of l's line block, in the plan's order); part[group][j] = the squared norms over the group's 256 lines
 __global__ __launch_bounds__(sp::SUPER) void resid_sym_combine_kernel(const SymCombineArgs p) {
-  __shared__ double red[sp::RPAD][4];
-  const int tid = threadIdx.x;
-  const int64_t l = (int64_t)blockIdx.x * sp::SUPER + tid;
+  const int64_t l = (int64_t)blockIdx.x * sp::SUPER + threadIdx.x;
   const bool in = l < p.P.n;
   const int L = in ? (int)(l / p.P.bs) : 0;
   const int64_t x = in ? l - (int64_t)L * p.P.bs : 0, sd = sp::slot_doubles(p.P);
-  for (int j = 0; j < p.r; ++j) {
-    double sq = 0.0;
-    if (in) {
-      double sum = 0.0;
-      for (int k = 0; k <= p.P.p; ++k) sum += p.slab[(int64_t)sp::contribution(p.P, L, k) * sd + (int64_t)j * p.P.bs + x];
-      const double v = p.B[l + (int64_t)j * p.ldb] - sum;
-      if (p.R) p.R[l + (int64_t)j * p.ldr] = v;
-      sq = v * v;
-    }
-    // a fixed butterfly inside the wave, then the four waves in order
-    sq += __shfl_xor(sq, 1);
-    sq += __shfl_xor(sq, 2);
-    sq += __shfl_xor(sq, 4);
-    sq += __shfl_xor(sq, 8);
-    sq += __shfl_xor(sq, 16);
-    sq += __shfl_xor(sq, 32);
-    if ((tid & 63) == 0) red[j][tid >> 6] = sq;
-  }
-  __syncthreads();
-  if (p.part && tid < p.r) p.part[(int64_t)blockIdx.x * sp::RPAD + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
+  tt::group_colnorms<sp::RPAD, sp::SUPER>(p.r, p.part, sp::RPAD, [&](int j) {
+    if (!in) return 0.0;
+    double sum = 0.0;
+    for (int k = 0; k <= p.P.p; ++k) sum += p.slab[(int64_t)sp::contribution(p.P, L, k) * sd + (int64_t)j * p.P.bs + x];
+    const double v = p.B[l + (int64_t)j * p.ldb] - sum;
+    if (p.R) p.R[l + (int64_t)j * p.ldr] = v;
+    return v;
+  });
 }
 
 // the two-pass route's last step: W = U X + U^T X counted the diagonal twice.  Rout(l, j) = B(l, j) - (W(l, j) - A(l, l) X(l, j)); part as above,
@@ -270,37 +242,15 @@ __global__ __launch_bounds__(sp::SUPER) void resid_sym_combine_kernel(const SymC
 __global__ __launch_bounds__(sp::SUPER) void resid_sym_finish_kernel(const double* __restrict__ W, const double* __restrict__ A, int64_t lda,
                                                                      const double* __restrict__ X, int64_t ldx, const double* B, int64_t ldb, double* R,
                                                                      int64_t ldr, double* __restrict__ part, int64_t n, int r) {
-  __shared__ double red[CAPI_TS_MAX_RHS][4];
-  const int tid = threadIdx.x;
-  const int64_t l = (int64_t)blockIdx.x * sp::SUPER + tid;
+  const int64_t l = (int64_t)blockIdx.x * sp::SUPER + threadIdx.x;
   const bool in = l < n;
   const double d = in ? A[l + l * lda] : 0.0;
-  for (int j = 0; j < r; ++j) {
-    double sq = 0.0;
-    if (in) {
-      const double v = B[l + (int64_t)j * ldb] - (W[l + (int64_t)j * n] - d * X[l + (int64_t)j * ldx]);
-      if (R) R[l + (int64_t)j * ldr] = v;
-      sq = v * v;
-    }
-    sq += __shfl_xor(sq, 1);
-    sq += __shfl_xor(sq, 2);
-    sq += __shfl_xor(sq, 4);
-    sq += __shfl_xor(sq, 8);
-    sq += __shfl_xor(sq, 16);
-    sq += __shfl_xor(sq, 32);
-    if ((tid & 63) == 0) red[j][tid >> 6] = sq;
-  }
-  __syncthreads();
-  if (part && tid < r) part[(int64_t)blockIdx.x * CAPI_TS_MAX_RHS + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
-}
-
-// colnorm2[j] = part[group 0][j] + part[group 1][j] + ..  (groups of `stride` doubles)
-__global__ __launch_bounds__(64) void resid_sym_norms_kernel(const double* __restrict__ part, int64_t groups, int stride, int r, double* __restrict__ colnorm2) {
-  const int j = threadIdx.x;
-  if (j >= r) return;
-  double sum = 0.0;
-  for (int64_t g = 0; g < groups; ++g) sum += part[g * stride + j];
-  colnorm2[j] = sum;
+  tt::group_colnorms<CAPI_TS_MAX_RHS, sp::SUPER>(r, part, CAPI_TS_MAX_RHS, [&](int j) {
+    if (!in) return 0.0;
+    const double v = B[l + (int64_t)j * ldb] - (W[l + (int64_t)j * n] - d * X[l + (int64_t)j * ldx]);
+    if (R) R[l + (int64_t)j * ldr] = v;
+    return v;
+  });
 }
 
 // From this many columns on the call takes the two-pass route: capi_dtrmm_thin NOTRANS and TRANS over the same triangle (read twice), then the
@@ -315,12 +265,12 @@ extern "C" {
 int capi_dresid_sym(capi_handle_t h, int64_t n, int64_t r, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B, int64_t ldb,
                     double* Rout, int64_t ldr, double* colnorm2) {
   CAPI_REQUIRE(h, h, "null handle");
-  CAPI_REQUIRE(h, r >= 1 && r <= CAPI_TS_MAX_RHS, "r: 1 <= r <= CAPI_TS_MAX_RHS (32) right-hand sides per call");
+  CAPI_REQUIRE_THIN_R(h, r);
   CAPI_REQUIRE(h, n >= 0 && n < (1LL << 31) && lda < (1LL << 24), "n / lda (lda < 2^24: 32 columns are addressed by 32-bit byte offsets)");
   CAPI_REQUIRE(h, n == 0 || (A && X && B && lda >= n && ldx >= n && ldb >= n && (!Rout || ldr >= n)), "A/lda/X/ldx/B/ldb/Rout/ldr");
   CAPI_REQUIRE(h, !Rout || Rout != X, "Rout must not alias X");
   if (n == 0) {
-    if (colnorm2) hipLaunchKernelGGL(resid_sym_norms_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)nullptr, (int64_t)0, sp::RPAD, (int)r, colnorm2);
+    if (colnorm2) hipLaunchKernelGGL(tt::colnorms_kernel<>, dim3(1), dim3(64), 0, h->stream, (const double*)nullptr, (int64_t)0, sp::RPAD, (int)r, colnorm2);
     CAPI_HIP_CHECK(h, hipGetLastError());
     return CAPI_OK;
   }
@@ -338,12 +288,11 @@ int capi_dresid_sym(capi_handle_t h, int64_t n, int64_t r, const double* A, int6
     if (rc != CAPI_OK) return rc;
     hipLaunchKernelGGL(resid_sym_finish_kernel, dim3((unsigned)groups), dim3(sp::SUPER), 0, h->stream, (const double*)W, A, lda, X, ldx, B, ldb, Rout, ldr,
                        colnorm2 ? part : (double*)nullptr, n, (int)r);
-    if (colnorm2) hipLaunchKernelGGL(resid_sym_norms_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)part, groups, (int)CAPI_TS_MAX_RHS, (int)r, colnorm2);
+    if (colnorm2) hipLaunchKernelGGL(tt::colnorms_kernel<>, dim3(1), dim3(64), 0, h->stream, (const double*)part, groups, (int)CAPI_TS_MAX_RHS, (int)r, colnorm2);
     CAPI_HIP_CHECK(h, hipGetLastError());
     return CAPI_OK;
   }
-  const int cus = h->cu_of[h->cur] > 0 ? h->cu_of[h->cur] : h->num_cu;
-  const sp::Plan P = sp::make_plan(n, cus);
+  const sp::Plan P = sp::make_plan(n, capi_stream_cus(h));
   void* pv = nullptr;
   int rc = capi_ws_get(h, sizeof(double) * (size_t)(sp::slab_doubles(P) + groups * sp::RPAD), &pv);
   if (rc != CAPI_OK) return rc;
@@ -360,7 +309,7 @@ int capi_dresid_sym(capi_handle_t h, int64_t n, int64_t r, const double* A, int6
   cp.ldb = ldb; cp.ldr = ldr;
   cp.r = (int)r; cp.P = P;
   hipLaunchKernelGGL(resid_sym_combine_kernel, dim3((unsigned)groups), dim3(sp::SUPER), 0, h->stream, cp);
-  if (colnorm2) hipLaunchKernelGGL(resid_sym_norms_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)part, groups, sp::RPAD, (int)r, colnorm2);
+  if (colnorm2) hipLaunchKernelGGL(tt::colnorms_kernel<>, dim3(1), dim3(64), 0, h->stream, (const double*)part, groups, sp::RPAD, (int)r, colnorm2);
   CAPI_HIP_CHECK(h, hipGetLastError());
   return CAPI_OK;
 }

@@ -13,15 +13,10 @@
 // lasts as long as its largest block: no block holds more than bs x bs elements, and bs < n / p + 32.  The p diagonal blocks hold half as much;
 // pairing them would free p / 2 CUs, which admits no larger p at 256 CUs (22: 253 blocks; 23 would need 276 - 11), so they are left alone.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define STP_HD __host__ __device__
-#else
-#define STP_HD
-#endif
+#include "thin_plan_common.h"
 
 namespace sym_thin_plan {
+using namespace thin_plan;
 
 constexpr int STRIP = 32;         // lines per wave strip: bs is a multiple
 constexpr int SUPER = 256;        // lines per super-tile edge (8 strips)
@@ -32,16 +27,13 @@ struct Plan {
   int p;                          // line blocks
 };
 
-STP_HD inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-STP_HD inline int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
-
 // the largest q with q (q + 1) / 2 <= cus (at least 1)
-STP_HD inline int max_blocks_edge(int cus) {
+THIN_HD inline int max_blocks_edge(int cus) {
   int q = 1;
   while ((q + 1) * (q + 2) / 2 <= cus) ++q;
   return q;
 }
-STP_HD inline Plan make_plan(int64_t n, int cus) {
+THIN_HD inline Plan make_plan(int64_t n, int cus) {
   Plan P;
   P.n = n;
   const int q = max_blocks_edge(cus);
@@ -49,32 +41,32 @@ STP_HD inline Plan make_plan(int64_t n, int cus) {
   P.p = (int)cdiv64(n, P.bs);
   return P;
 }
-STP_HD inline int num_blocks(const Plan& P) { return P.p * (P.p + 1) / 2; }
-STP_HD inline int block_id(int I, int J) { return J * (J + 1) / 2 + I; }
-STP_HD inline void block_of(int id, int* I, int* J) {
+THIN_HD inline int num_blocks(const Plan& P) { return P.p * (P.p + 1) / 2; }
+THIN_HD inline int block_id(int I, int J) { return J * (J + 1) / 2 + I; }
+THIN_HD inline void block_of(int id, int* I, int* J) {
   int j = 0;
   while ((j + 1) * (j + 2) / 2 <= id) ++j;
   *J = j;
   *I = id - j * (j + 1) / 2;
 }
 // lines [l0, l1) of line block L
-STP_HD inline int64_t line0(const Plan& P, int L) { return (int64_t)L * P.bs; }
-STP_HD inline int64_t line1(const Plan& P, int L) { return min64(P.n, (int64_t)(L + 1) * P.bs); }
+THIN_HD inline int64_t line0(const Plan& P, int L) { return (int64_t)L * P.bs; }
+THIN_HD inline int64_t line1(const Plan& P, int L) { return min64(P.n, (int64_t)(L + 1) * P.bs); }
 // the two slots a block writes: which = 0 the lines of I, which = 1 the lines of J
-STP_HD inline int slot_of(int I, int J, int which) { return 2 * block_id(I, J) + which; }
-STP_HD inline int64_t slot_doubles(const Plan& P) { return (int64_t)RPAD * P.bs; }
-STP_HD inline int64_t slab_doubles(const Plan& P) { return 2 * (int64_t)num_blocks(P) * slot_doubles(P); }
+THIN_HD inline int slot_of(int I, int J, int which) { return 2 * block_id(I, J) + which; }
+THIN_HD inline int64_t slot_doubles(const Plan& P) { return (int64_t)RPAD * P.bs; }
+THIN_HD inline int64_t slab_doubles(const Plan& P) { return 2 * (int64_t)num_blocks(P) * slot_doubles(P); }
 // contribution k = 0 .. p of line block L, in the order the combine adds them
-STP_HD inline int contribution(const Plan& P, int L, int k) {
+THIN_HD inline int contribution(const Plan& P, int L, int k) {
   const int nrow = P.p - L;                                   // row slots of (L, L .. p - 1)
   return k < nrow ? slot_of(L, L + k, 0) : slot_of(k - nrow, L, 1);
 }
 // elements of A that block (I, J) reads
-STP_HD inline int64_t block_elems(const Plan& P, int I, int J) {
+THIN_HD inline int64_t block_elems(const Plan& P, int I, int J) {
   const int64_t a = line1(P, I) - line0(P, I), b = line1(P, J) - line0(P, J);
   return I == J ? a * (a + 1) / 2 : a * b;
 }
 // the block that owns element (row, col), row <= col
-STP_HD inline int owner(const Plan& P, int64_t row, int64_t col) { return block_id((int)(row / P.bs), (int)(col / P.bs)); }
+THIN_HD inline int owner(const Plan& P, int64_t row, int64_t col) { return block_id((int)(row / P.bs), (int)(col / P.bs)); }
 
 }  // namespace sym_thin_plan

@@ -8,14 +8,10 @@
 // lines of a triangle have lengths 1..n.  A workgroup walks its consecutive tiles; the 256 x rpad partial sums of every group of lines it
 // touches go to a slab of its own, and a second launch adds a group's slabs in slice order: no floating-point atomics, the same bits on every run.
 // The thin operand is stationary in LDS, 256 contraction indices at a time in two halves: the next block is fetched while the last tile of the
-// current one is multiplied, one barrier per block.  T's pieces are double-buffered in registers, one tile (8 x 16 bytes per lane) ahead, as
-// resid_ts_kernel has them.
-//   NOTRANS (row dots): lane (r16, g) of wave w loads rows 2 r16, + 1 of its 32-row strip of columns 4 s + g -- 16 lanes fetch 256 bytes of a column.
-//   TRANS (column dots): lane (c16, g) loads row pairs 8 q + 2 g, + 1 of ITS OWN column of two 16-column strips; the k index of the MFMA is dealt
-//   to suit the loads, as gemtn_ts_kernel does.
-// Alignment: a packed column starts at x (x + 1) / 2, so every other pair of columns is 8-byte aligned only.  The steady loop loads 16 bytes from
-// such a column all the same: global loads of gfx950 need dword alignment only, and the vector type below is declared 8-byte aligned so that
-// the compiler may not assume more.  (An odd column costs one more 128-byte line per 256-byte run; no column falls back to scalar loads.)
+// current one is multiplied, one barrier per block.  T's pieces are double-buffered in registers, one tile (8 x 16 bytes per lane) ahead.  A wave's
+// 32 x 32 part of a tile is multiplied in the row-dot form of thin_tile.h for NOTRANS and in its column-dot form for TRANS.
+// Alignment: a packed column starts at x (x + 1) / 2, so every other pair of columns is 8-byte aligned only; the steady loop loads 16 bytes from
+// such a column all the same (d2u_t of thin_tile.h); no column falls back to scalar loads.
 // Measured (profiles/cholinv_solve.txt, n = 32768): packed against full storage costs 1.2 x for NOTRANS and 1.4 x for TRANS, misaligned loads and
 // the 64-bit column address together; a peeled head element with aligned loads behind it is not built.
 // Offsets into the packed triangle are 64-bit throughout: column 65536 starts beyond 2^31 doubles.
@@ -23,15 +19,16 @@
 // nothing below the diagonal or outside the block takes part, whatever it holds.
 #include <type_traits>
 #include "capi_internal.h"
+#include "thin_tile.h"
 #include "tri_thin_plan.h"
 
 namespace {
 
 namespace tp = tri_thin_plan;
-
-typedef double d4_t __attribute__((ext_vector_type(4)));
-typedef double d2_t __attribute__((ext_vector_type(2)));
-typedef d2_t d2u_t __attribute__((aligned(8)));      // a row pair of a column that is 8-byte aligned only
+namespace tt = thin_tile;
+using tt::d2_t;
+using tt::d2u_t;
+using tt::d4_t;
 
 constexpr int TT_THREADS = 512;                 // 8 waves, one workgroup per CU
 constexpr int TT_BLK = tp::GROUP;               // contraction indices of the thin operand per LDS half (8 tiles)
@@ -79,8 +76,7 @@ __global__ __launch_bounds__(TT_THREADS) void trmm_thin_kernel(const ThinArgs p)
     }
   };
 
-  // ---- T's piece of tile (g, c) for this lane ----
-  // NOTRANS: rows 256 g + 32 w + 2 l16, + 1 of columns 32 c + 4 q + g4.   TRANS: rows 32 c + 8 (q & 3) + 2 g4, + 1 of column 256 g + 32 w + 16 (q >> 2) + l16
+  // ---- T's piece q of tile (g, c) for this lane: wave w's 32 lines of group g x the tile's 32 contraction indices ----
   auto piece = [&](int64_t g, int64_t c, int q, int64_t* row, int64_t* col) {
     if (!TR) { *row = tp::GROUP * g + 32 * w + 2 * l16; *col = tp::DEPTH * c + 4 * q + g4; }
     else { *row = tp::DEPTH * c + 8 * (q & 3) + 2 * g4; *col = tp::GROUP * g + 32 * w + 16 * (q >> 2) + l16; }
@@ -128,29 +124,8 @@ __global__ __launch_bounds__(TT_THREADS) void trmm_thin_kernel(const ThinArgs p)
   auto multiply = [&](const double* L, int64_t c, const d2_t (&cur)[TT_NP]) {
     const int kb = (int)(c & (tp::CPG - 1)) * tp::DEPTH;                  // the tile's place inside the LDS block
     __builtin_amdgcn_s_setprio(1);
-    if (!TR) {
-      // acc[h][rb]: lane (l16, g4) holds (T B)(32 w + 2 l16 + h, 16 rb + g4 + 4 reg)
-      const double* lx = L + (kb + g4) * 16 + l16;
-#pragma unroll
-      for (int q = 0; q < TT_NP; ++q)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-          const double xv = lx[(rb * TT_BLK + 4 * q) * 16];
-          acc[0][rb] = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, cur[q].x, acc[0][rb], 0, 0, 0);
-          acc[1][rb] = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, cur[q].y, acc[1][rb], 0, 0, 0);
-        }
-    } else {
-      // acc[t][rb]: lane (l16, g4) holds (T^T B)(32 w + 16 t + g4 + 4 reg, 16 rb + l16)
-      const double* lx = L + (kb + 2 * g4) * 16 + l16;
-#pragma unroll
-      for (int q = 0; q < TT_NP; ++q)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-          const double b0 = lx[(rb * TT_BLK + 8 * (q & 3)) * 16], b1 = lx[(rb * TT_BLK + 8 * (q & 3) + 1) * 16];
-          acc[q >> 2][rb] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[q].x, b0, acc[q >> 2][rb], 0, 0, 0);
-          acc[q >> 2][rb] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[q].y, b1, acc[q >> 2][rb], 0, 0, 0);
-        }
-    }
+    if (!TR) tt::mfma_row_dots<RB>(acc, L + (kb + g4) * 16 + l16, TT_BLK * 16, cur);
+    else tt::mfma_col_dots<RB>(acc, L + (kb + 2 * g4) * 16 + l16, TT_BLK * 16, cur);
     __builtin_amdgcn_s_setprio(0);
   };
   // the group's partial sums: slab slot s + g (unique: the slices' tile ranges are consecutive), [16 RB columns][256 lines]
@@ -247,7 +222,7 @@ extern "C" {
 int capi_dtrmm_thin(capi_handle_t h, int shape, int trans, int64_t m, int64_t n, int64_t r, double alpha, const double* T, int64_t ldt, int64_t col0,
                     const double* B, int64_t ldb, double beta, double* C, int64_t ldc) {
   CAPI_REQUIRE(h, h, "null handle");
-  CAPI_REQUIRE(h, r >= 1 && r <= CAPI_TS_MAX_RHS, "r: 1 <= r <= CAPI_TS_MAX_RHS (32) columns per call");
+  CAPI_REQUIRE_THIN_R(h, r);
   CAPI_REQUIRE(h, shape == CAPI_RECT || shape == CAPI_UPPERTRI, "shape: CAPI_RECT or CAPI_UPPERTRI");
   CAPI_REQUIRE(h, trans == CAPI_NOTRANS || trans == CAPI_TRANS, "trans");
   CAPI_REQUIRE(h, m >= 0 && n >= 0 && m < (1LL << 31) && n < (1LL << 31), "m / n");
@@ -258,11 +233,10 @@ int capi_dtrmm_thin(capi_handle_t h, int shape, int trans, int64_t m, int64_t n,
   CAPI_REQUIRE(h, lines == 0 || C, "C");
   CAPI_REQUIRE(h, lines == 0 || depth == 0 || (T && B && B != C), "T / B (C must not alias B)");
   if (lines == 0) return CAPI_OK;
-  const int rb = r > 16 ? 2 : 1, rpad = 16 * rb;
+  const int rb = capi_thin_rb(r), rpad = 16 * rb;
   CombineArgs cp;
   cp.P = tp::make_plan(shape == CAPI_UPPERTRI ? tp::UPPERTRI : tp::RECT, trans, m, n);
-  int cus = h->cu_of[h->cur] > 0 ? h->cu_of[h->cur] : h->num_cu;
-  const int S = tp::make_slices(cp.P, cus, cp.pos);
+  const int S = tp::make_slices(cp.P, capi_stream_cus(h), cp.pos);
   double* slab = nullptr;
   if (S > 0) {
     void* pv = nullptr;

@@ -11,15 +11,10 @@
 // s / S of the block's elements, so no slice holds more than the mean share plus ONE TILE's worth (256 x 32 elements); a slice may be
 // empty when a single tile outweighs the mean share.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define TTP_HD __host__ __device__
-#else
-#define TTP_HD
-#endif
+#include "thin_plan_common.h"
 
 namespace tri_thin_plan {
+using namespace thin_plan;
 
 constexpr int GROUP = 256;        // output lines per group
 constexpr int DEPTH = 32;         // contraction indices per tile
@@ -35,17 +30,13 @@ struct Plan {
 };
 
 // first element of column x of a packed upper triangle (structure.h uppertri).  The even factor is halved first: exact up to x ~ 4e9
-TTP_HD inline int64_t packed_col_start(int64_t x) { return (x & 1) ? x * ((x + 1) / 2) : (x / 2) * (x + 1); }
+THIN_HD inline int64_t packed_col_start(int64_t x) { return (x & 1) ? x * ((x + 1) / 2) : (x / 2) * (x + 1); }
 // block column j of a view whose first column is the triangle's column col0, relative to the view's first element
-TTP_HD inline int64_t packed_col_offset(int64_t col0, int64_t j) { return packed_col_start(col0 + j) - packed_col_start(col0); }
+THIN_HD inline int64_t packed_col_offset(int64_t col0, int64_t j) { return packed_col_start(col0 + j) - packed_col_start(col0); }
 // alignment class of a column that starts `start` doubles behind a 16-byte boundary: 0 = 16-byte aligned, 1 = 8-byte aligned only
-TTP_HD inline int align_class(int64_t start) { return (int)(start & 1); }
+THIN_HD inline int align_class(int64_t start) { return (int)(start & 1); }
 
-TTP_HD inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-TTP_HD inline int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
-TTP_HD inline int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
-
-TTP_HD inline Plan make_plan(int shape, int trans, int64_t m, int64_t n) {
+THIN_HD inline Plan make_plan(int shape, int trans, int64_t m, int64_t n) {
   Plan P;
   P.tri = shape == UPPERTRI; P.trans = trans != 0; P.m = m; P.n = n;
   P.lines = trans ? n : m; P.depth = trans ? m : n;
@@ -53,20 +44,20 @@ TTP_HD inline Plan make_plan(int shape, int trans, int64_t m, int64_t n) {
   return P;
 }
 // contraction index (in tiles) of the first tile of group g: the triangle's rows 256 g.. start at column 256 g
-TTP_HD inline int64_t first_tile(const Plan& P, int64_t g) { return (P.tri && !P.trans) ? CPG * g : 0; }
-TTP_HD inline int64_t group_tiles(const Plan& P, int64_t g) {
+THIN_HD inline int64_t first_tile(const Plan& P, int64_t g) { return (P.tri && !P.trans) ? CPG * g : 0; }
+THIN_HD inline int64_t group_tiles(const Plan& P, int64_t g) {
   if (!P.tri) return P.kc;
   return P.trans ? min64(P.kc, CPG * (g + 1)) : P.kc - CPG * g;
 }
 // tiles of the groups before g (0 <= g <= ngroups)
-TTP_HD inline int64_t tiles_before(const Plan& P, int64_t g) {
+THIN_HD inline int64_t tiles_before(const Plan& P, int64_t g) {
   if (!P.tri) return g * P.kc;
   if (!P.trans) return g * P.kc - (CPG / 2) * g * (g - 1);
   return g < P.ngroups ? (CPG / 2) * g * (g + 1) : (P.ngroups > 0 ? (CPG / 2) * (P.ngroups - 1) * P.ngroups + P.kc : 0);
 }
-TTP_HD inline int64_t total_tiles(const Plan& P) { return (P.lines > 0 && P.depth > 0) ? tiles_before(P, P.ngroups) : 0; }
+THIN_HD inline int64_t total_tiles(const Plan& P) { return (P.lines > 0 && P.depth > 0) ? tiles_before(P, P.ngroups) : 0; }
 // tile number pos -> (group, contraction index in tiles)
-TTP_HD inline void locate(const Plan& P, int64_t pos, int64_t* g, int64_t* c) {
+THIN_HD inline void locate(const Plan& P, int64_t pos, int64_t* g, int64_t* c) {
   int64_t lo = 0, hi = P.ngroups - 1;
   while (lo < hi) {
     const int64_t mid = (lo + hi + 1) / 2;
@@ -76,12 +67,12 @@ TTP_HD inline void locate(const Plan& P, int64_t pos, int64_t* g, int64_t* c) {
   *c = first_tile(P, lo) + (pos - tiles_before(P, lo));
 }
 // the tile's rows [r0, r1) and columns [c0, c1) of the block
-TTP_HD inline void tile_rect(const Plan& P, int64_t g, int64_t c, int64_t* r0, int64_t* r1, int64_t* c0, int64_t* c1) {
+THIN_HD inline void tile_rect(const Plan& P, int64_t g, int64_t c, int64_t* r0, int64_t* r1, int64_t* c0, int64_t* c1) {
   if (!P.trans) { *r0 = GROUP * g; *r1 = min64(P.m, *r0 + GROUP); *c0 = DEPTH * c; *c1 = min64(P.n, *c0 + DEPTH); }
   else { *c0 = GROUP * g; *c1 = min64(P.n, *c0 + GROUP); *r0 = DEPTH * c; *r1 = min64(P.m, *r0 + DEPTH); }
 }
 // elements of the block inside the tile
-TTP_HD inline int64_t tile_elems(const Plan& P, int64_t g, int64_t c) {
+THIN_HD inline int64_t tile_elems(const Plan& P, int64_t g, int64_t c) {
   int64_t r0, r1, c0, c1;
   tile_rect(P, g, c, &r0, &r1, &c0, &c1);
   if (!P.tri || r1 - 1 <= c0) return (r1 - r0) * (c1 - c0);
@@ -90,7 +81,7 @@ TTP_HD inline int64_t tile_elems(const Plan& P, int64_t g, int64_t c) {
   return e;
 }
 // how many consecutive tiles of group g, from c on, are known to weigh the same as tile c (>= 1): the interior of a group
-TTP_HD inline int64_t run_length(const Plan& P, int64_t g, int64_t c) {
+THIN_HD inline int64_t run_length(const Plan& P, int64_t g, int64_t c) {
   const int64_t last = first_tile(P, g) + group_tiles(P, g) - 1;        // may be ragged along the contraction index
   int64_t end = last;                                                  // first tile that may weigh differently
   if (P.tri && !P.trans && c < CPG * (g + 1)) return 1;                // tiles that the diagonal crosses

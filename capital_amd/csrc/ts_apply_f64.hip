@@ -15,17 +15,19 @@
 // strips per wave) of 32-row chunks; the chunk of B is staged through LDS once per workgroup.  Workgroup z of S takes the chunks
 // z, z + S, ..; its partial sums go to slab z, and a second launch adds the slabs in the order z = 0, 1, ..: no floating-point
 // atomics, the same bits on every run.
-// capi_dresid_ts: X stays in LDS ([k][16] planes, one per 16 right-hand sides); a wave owns 32-row tiles of A and, as trmm_right_ts32
-// does, multiplies rows 2 i and 2 i + 1 in two accumulator sets, so that a lane loads and stores 16 bytes of two consecutive rows.
+// capi_dresid_ts: X stays in LDS ([k][16] planes, one per 16 right-hand sides); a wave owns 32-row tiles of A and multiplies them in the
+// row-dot form of thin_tile.h, so that a lane loads and stores 16 bytes of two consecutive rows.
 // n beyond what LDS holds (1024 columns at r <= 16, 512 beyond) goes in column blocks whose X is restaged per round of tiles: A is
 // still read once.  The squared norms are summed per lane, per wave (a fixed butterfly) and per worker slot, then in slot order.
 #include <type_traits>
 #include "capi_internal.h"
+#include "thin_tile.h"
 
 namespace {
 
-typedef double d4_t __attribute__((ext_vector_type(4)));
-typedef double d2_t __attribute__((ext_vector_type(2)));
+namespace tt = thin_tile;
+using tt::d2_t;
+using tt::d4_t;
 
 constexpr int TA_THREADS = 512;          // 8 waves, one workgroup per CU
 constexpr int TA_RUN = 8;                // rows of its column a lane takes per chunk of capi_dgemtn_ts (four 16-byte pairs)
@@ -283,15 +285,7 @@ __global__ __launch_bounds__(TA_THREADS) void resid_ts_kernel(const ResidArgs p)
     else if (has_next) aload_edge(ni, ncb, nb, nxt);
     const double* lx = Lx + (b * TA_BATCH + g) * 16 + r16;
     __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int s = 0; s < TA_KS; ++s) {
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb) {
-        const double xv = lx[rb * p.kb * 16 + 64 * s];
-        acc[0][rb] = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, cur[s].x, acc[0][rb], 0, 0, 0);
-        acc[1][rb] = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, cur[s].y, acc[1][rb], 0, 0, 0);
-      }
-    }
+    tt::mfma_row_dots<RB>(acc, lx, p.kb * 16, cur);
     __builtin_amdgcn_s_setprio(0);
     if (b == nbatch - 1 && cb == p.nblk - 1) epilogue(i);
   };
@@ -317,23 +311,10 @@ __global__ __launch_bounds__(TA_THREADS) void resid_ts_kernel(const ResidArgs p)
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
-        double v = nrm[rb][reg];
-        v += __shfl_xor(v, 1);
-        v += __shfl_xor(v, 2);
-        v += __shfl_xor(v, 4);
-        v += __shfl_xor(v, 8);
+        const double v = tt::butterfly_sum<16>(nrm[rb][reg]);
         if (r16 == 0) p.part[((int64_t)blockIdx.x * 8 + w) * 32 + 16 * rb + g + 4 * reg] = v;
       }
   }
-}
-
-// colnorm2[j] = part[slot 0][j] + part[slot 1][j] + ..  (slots of 32 doubles, of which the first rpad were written)
-__global__ __launch_bounds__(64) void resid_ts_norms_kernel(const double* __restrict__ part, int slots, int r, double* __restrict__ colnorm2) {
-  const int j = threadIdx.x;
-  if (j >= r) return;
-  double sum = 0.0;
-  for (int s = 0; s < slots; ++s) sum += part[(int64_t)s * 32 + j];
-  colnorm2[j] = sum;
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -345,11 +326,11 @@ extern "C" {
 int capi_dgemtn_ts(capi_handle_t h, int64_t m, int64_t n, int64_t r, double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
                    double beta, double* C, int64_t ldc) {
   CAPI_REQUIRE(h, h, "null handle");
-  CAPI_REQUIRE(h, r >= 1 && r <= CAPI_TS_MAX_RHS, "r: 1 <= r <= CAPI_TS_MAX_RHS (32) right-hand sides per call");
+  CAPI_REQUIRE_THIN_R(h, r);
   CAPI_REQUIRE(h, m >= 0 && m < (1LL << 35) && n >= 1 && n <= 65535LL * TA_GROUP, "m / n (m < 2^35 rows, n <= 65535 * 256 columns: the grid's limits)");
   CAPI_REQUIRE(h, C && ldc >= n, "C/ldc");
   CAPI_REQUIRE(h, m == 0 || (A && B && lda >= m && ldb >= m), "A/lda/B/ldb");
-  const int rb = r > 16 ? 2 : 1, rpad = 16 * rb;
+  const int rb = capi_thin_rb(r), rpad = 16 * rb;
   const int64_t nchunk = cdiv(m, TA_CHUNK), ncg = cdiv(n, TA_GROUP);
   int64_t S = h->num_cu / ncg;
   if (S < 1) S = 1;
@@ -378,11 +359,11 @@ int capi_dgemtn_ts(capi_handle_t h, int64_t m, int64_t n, int64_t r, double alph
 int capi_dresid_ts(capi_handle_t h, int64_t m, int64_t n, int64_t r, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B,
                    int64_t ldb, double* Rout, int64_t ldr, double* colnorm2) {
   CAPI_REQUIRE(h, h, "null handle");
-  CAPI_REQUIRE(h, r >= 1 && r <= CAPI_TS_MAX_RHS, "r: 1 <= r <= CAPI_TS_MAX_RHS (32) right-hand sides per call");
+  CAPI_REQUIRE_THIN_R(h, r);
   CAPI_REQUIRE(h, m >= 0 && m < (1LL << 35) && n >= 1 && n <= 65535LL * TA_GROUP, "m / n (m < 2^35 rows, n <= 65535 * 256 columns: the grid's limits)");
   CAPI_REQUIRE(h, X && ldx >= n, "X/ldx");
   CAPI_REQUIRE(h, m == 0 || (A && B && lda >= m && ldb >= m && (!Rout || ldr >= m)), "A/lda/B/ldb/Rout/ldr");
-  const int rb = r > 16 ? 2 : 1;
+  const int rb = capi_thin_rb(r);
   const int64_t ntile = cdiv(m, TA_TILE), nround = cdiv(ntile, 8);
   int64_t G = nround < h->num_cu ? nround : h->num_cu;
   double* part = nullptr;
@@ -411,7 +392,8 @@ int capi_dresid_ts(capi_handle_t h, int64_t m, int64_t n, int64_t r, const doubl
       hipLaunchKernelGGL(resid_ts_kernel<2>, dim3((unsigned)G), dim3(TA_THREADS), lds, h->stream, p);
     }
   }
-  if (colnorm2) hipLaunchKernelGGL(resid_ts_norms_kernel, dim3(1), dim3(64), 0, h->stream, part, (int)(G * 8), (int)r, colnorm2);
+  // slots of 32 doubles, of which the first rpad were written
+  if (colnorm2) hipLaunchKernelGGL(tt::colnorms_kernel<>, dim3(1), dim3(64), 0, h->stream, (const double*)part, G * 8, 32, (int)r, colnorm2);
   CAPI_HIP_CHECK(h, hipGetLastError());
   return CAPI_OK;
 }
