@@ -40,6 +40,7 @@ _SIGS = {
     "capi_dgemtn_ts": [_i64, _i64, _i64, _dbl, _vp, _i64, _vp, _i64, _dbl, _vp, _i64],
     "capi_dresid_ts": [_i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
     "capi_dtrmm_thin": [_int, _int, _i64, _i64, _i64, _dbl, _vp, _i64, _i64, _vp, _i64, _dbl, _vp, _i64],
+    "capi_dtrsm_thin": [_int, _i64, _i64, _vp, _i64, _i64, _vp, _i64],
     "capi_dresid_sym": [_i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
     "capi_get_info": [C.POINTER(_int)],
     "capi_reset_info": [],

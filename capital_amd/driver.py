@@ -54,6 +54,7 @@ def bind(D):
     D.capital_cholinv_dims.argtypes = [_vp, C.POINTER(_i64)] + [C.POINTER(_int)] * 5
     D.capital_cholinv_stats.argtypes = [_vp] + [C.POINTER(_i64)] * 3
     D.capital_cholinv_set_trsm_mode.argtypes = [_vp, _int]
+    D.capital_cholinv_set_solve_substitution.argtypes = [_vp, _int]
     D.capital_cholinv_solve.argtypes = [_vp, _i64, _dp, _dp, _dp, _int]
     D.capital_cacqr_create.argtypes = [_i64, _i64] + [_int] * 8
     D.capital_cacqr_create.restype = _vp
@@ -140,7 +141,7 @@ class Cholinv:
     Arguments in the order of the reference bench (bench/cholesky/cholinv.cpp:15-22)."""
 
     def __init__(self, n, c=1, complete_inv=0, split=1, bc_mult=0, layout=0, num_chunks=0, serialize=True, bc_policy=2, trsm_mode=False,
-                 flush_intermediates=False):
+                 flush_intermediates=False, substitution=False):
         self.D = load()
         self.p = self.D.capital_cholinv_create(n, c, layout, num_chunks, int(complete_inv), split, bc_mult,
                                                int(bool(serialize)) + (2 if flush_intermediates else 0), bc_policy)
@@ -148,6 +149,8 @@ class Cholinv:
             raise DriverError("capital_cholinv_create: " + self.D.capital_drv_last_error().decode())
         if trsm_mode:      # info::solve_with_trsm: potrf + block TRSM + SYRK, no inverse formed (not the reference's schedule)
             _ck(self.D.capital_cholinv_set_trsm_mode(self.p, 1), "set_trsm_mode")
+        if substitution:   # info::solve_by_substitution: solve() by two capi_dtrsm_thin calls on R, in either mode
+            self.set_solve_substitution(True)
         nloc, x, y, z, d, cc = _i64(), _int(), _int(), _int(), _int(), _int()
         _ck(self.D.capital_cholinv_dims(self.p, C.byref(nloc), C.byref(x), C.byref(y), C.byref(z), C.byref(d), C.byref(cc)), "dims")
         self.n, self.n_loc, self.x, self.y, self.z, self.d, self.c = n, nloc.value, x.value, y.value, z.value, d.value, cc.value
@@ -163,6 +166,10 @@ class Cholinv:
     def factor(self):
         _ck(self.D.capital_cholinv_factor(self.p), "factor")
 
+    def set_solve_substitution(self, on):
+        """info::solve_by_substitution for the solves that follow; the factors stay as they are (no new factor() is needed)."""
+        _ck(self.D.capital_cholinv_set_solve_substitution(self.p, int(bool(on))), "set_solve_substitution")
+
     def residual(self):
         v = _dbl()
         _ck(self.D.capital_cholinv_residual(self.p, C.byref(v)), "residual")
@@ -170,8 +177,8 @@ class Cholinv:
 
     def solve(self, B, refine=1, residual=True):
         """A X = B on the factors of the last factor() (cholesky::cholinv::solve, one rank): products with the resident R^-1 -- block-wise with
-        R^-1_11, R^-1_22 and R_12 where complete_inv=0 skipped R^-1_12 -- or capi_dtrsm on R in TRSM mode, then `refine` steps of
-        fixed-precision refinement.  B: n x r.  Returns (X, resnorms): X n x r; resnorms[j] = ||b_j - A x_j||_2, or None with residual=False.
+        R^-1_11, R^-1_22 and R_12 where complete_inv=0 skipped R^-1_12 -- or capi_dtrsm on R in TRSM mode, or, with substitution=True, two
+        thin triangular solves on R (capi_dtrsm_thin: either mode, packed or not, no inverse), then `refine` steps of fixed-precision refinement.  B: n x r.  Returns (X, resnorms): X n x r; resnorms[j] = ||b_j - A x_j||_2, or None with residual=False.
         Like factor(), the refinement and the residual norms read A's upper triangle alone (capi_dresid_sym): what set_A left below the diagonal is
         never used."""
         b = np.asfortranarray(B, dtype=np.float64)

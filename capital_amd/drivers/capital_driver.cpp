@@ -38,6 +38,7 @@ struct cholinv_problem {
   virtual void dims(int64_t* nloc, int* x, int* y, int* z, int* d, int* c) = 0;
   virtual void stats(int64_t* bc, int64_t* levels, int64_t* bcdim) = 0;
   virtual void set_trsm_mode(bool on) = 0;
+  virtual void set_solve_substitution(bool on) = 0;
   virtual void solve(int64_t r, const double* B_host, double* X_host, double* resnorm_host, int refine) = 0;
 };
 
@@ -77,6 +78,7 @@ struct cholinv_impl : cholinv_problem {
   }
   void stats(int64_t* bc, int64_t* levels, int64_t* bcdim) override { *bc = pack.num_base_cases; *levels = pack.num_levels; *bcdim = pack.bcDimension; }
   void set_trsm_mode(bool on) override { pack.solve_with_trsm = on; }
+  void set_solve_substitution(bool on) override { pack.solve_by_substitution = on; }
   // A X = B on the factors of the last factor(): B_host n x r column-major, X_host receives n x r, resnorm_host (may be NULL: no residual
   // pass) the r norms ||b_j - A x_j||_2
   void solve(int64_t r, const double* B_host, double* X_host, double* resnorm_host, int refine) override {
@@ -236,6 +238,8 @@ int capital_cholinv_dims(void* p, int64_t* nloc, int* x, int* y, int* z, int* d,
 int capital_cholinv_stats(void* p, int64_t* bc, int64_t* levels, int64_t* bcdim) { return guarded([&] { ((cholinv_problem*)p)->stats(bc, levels, bcdim); }); }
 // TRSM mode (info::solve_with_trsm): potrf + block TRSM + SYRK recursion, no inverse formed (one GPU, or a d x d x c grid: potrf_rec_grid)
 int capital_cholinv_set_trsm_mode(void* p, int on) { return guarded([&] { ((cholinv_problem*)p)->set_trsm_mode(on != 0); }); }
+// info::solve_by_substitution: solve() by two thin triangular solves on R (capi_dtrsm_thin), in either mode; takes effect at the next solve()
+int capital_cholinv_set_solve_substitution(void* p, int on) { return guarded([&] { ((cholinv_problem*)p)->set_solve_substitution(on != 0); }); }
 // A X = B on the factors (cholesky::cholinv::solve): after capital_cholinv_factor, one rank; resnorm_host_or_null == NULL skips the residual pass.
 // Refinement and residual read A's upper triangle alone, as the factorization does: A need not be stored symmetric
 int capital_cholinv_solve(void* p, int64_t r, const double* B_host, double* X_host, double* resnorm_host_or_null, int refine) {

@@ -25,6 +25,8 @@
 #pragma weak capi_dtrmm_thin
 #pragma weak capi_dresid_ts
 #pragma weak capi_dresid_sym
+// .. and so is the thin triangular solve of info::solve_by_substitution: without it solve() runs as before and refuses only that flag
+#pragma weak capi_dtrsm_thin
 
 namespace cholesky {
 
@@ -65,6 +67,10 @@ public:
     // forms NO inverse: n^3/3 executed flops instead of 5 n^3/12.  R is the same factor; Rinv is not formed (construct_Rinv
     // throws).  One GPU, or a d x d x c grid (potrf_rec_grid).  Default off: the reference-exact schedule.
     bool solve_with_trsm = false;
+    // solve() by SUBSTITUTION on R (capi_dtrsm_thin, twice) instead of products with R^-1 (inverse mode) or the block TRSM (TRSM mode): row-wise
+    // backward stable without refinement, reads the packed or the rect R as it lies (no full-storage image: Serialize + FlushIntermediates
+    // solves in TRSM mode too), never touches Rinv.  May be switched between two solves on the same factors.  Default off.
+    bool solve_by_substitution = false;
     // LAPACK info of the factorisation (the reference drops it, lapack/interface.hpp:39,54): 0, or the 1-based position,
     // inside the first diagonal block that failed, of the first non-positive pivot.  factor() throws std::domain_error then.
     int potrf_info = 0;
@@ -224,6 +230,7 @@ public:
   //   complete_inv == 0 and the top level split at h1 (R^-1_12 was never formed):
   //       y1 = R11^-T b1,  y2 = R22^-T (b2 - R12^T y1),  x2 = R22^-1 y2,  x1 = R11^-1 (y1 - R12 x2)      -- the same bytes as the complete form
   //   TRSM mode (no inverse exists): X = R^-1 R^-T B by capi_dtrsm on a full-storage R (Rfull where resident, or the rect structure)
+  //   info::solve_by_substitution, either mode: X = R^-1 (R^-T B) by two capi_dtrsm_thin calls on R as it lies, packed or rect; no inverse is used
   // `refine` steps of fixed-precision refinement follow (rho = B - A X by capi_dresid_sym, X += solve(rho)): multiplying by an explicit inverse
   // is not backward stable in general, one step restores a backward error at the level of u for kappa u < 1.  The refinement and the residual
   // norms read A's UPPER triangle alone, as factor() does (capi_dresid_sym: a tile of the triangle serves the lines of its rows and, transposed,
@@ -235,6 +242,8 @@ public:
     constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
     if (CommInfo.size > 1) throw std::logic_error("cholinv::solve is built for one rank: on a grid the factors are element-cyclic (factor there, solve on one rank)");
     if (!&capi_dtrmm_thin || !&capi_dresid_ts) throw std::logic_error("cholinv: this C-ABI library has no capi_dtrmm_thin / capi_dresid_ts: no solve");
+    const bool subst = args.solve_by_substitution;
+    if (subst && !&capi_dtrsm_thin) throw std::logic_error("cholinv: this C-ABI library has no capi_dtrsm_thin: no solve by substitution");
     if (!args.factored || args.potrf_info != 0 || !args.R.filled() || (!args.solve_with_trsm && !args.Rinv.filled()))
       throw std::logic_error("cholinv::solve: factor() has not run or did not succeed: there are no valid factors to solve with");
     if (args.factored_trsm != args.solve_with_trsm)
@@ -243,7 +252,7 @@ public:
     if (r < 1 || B.num_rows_global() != n || B.num_rows_local() != n || A.num_rows_local() != n || A.num_columns_local() != n || refine < 0)
       throw std::invalid_argument("cholinv::solve: B must be n x r with r >= 1 (matrix(r, n, 1, 1)), A the factored matrix, refine >= 0");
     const double* Rfullp = nullptr;
-    if (args.solve_with_trsm) {
+    if (args.solve_with_trsm && !subst) {
       // (FlushIntermediates promises that no full-storage working image outlives factor(): none is relied on there, whatever is still allocated)
       Rfullp = packed ? (IP::keep_arena && args.Rfull.filled() ? args.Rfull.data() : nullptr) : (const double*)args.R.data();
       if (!Rfullp)
@@ -254,10 +263,10 @@ public:
     capi_handle_t h = capital::handle();
     CAPITAL_CHECK(capi_stream_select(h, 0));
     const int64_t W = CAPI_TS_MAX_RHS, h1 = args.top_split;
-    const bool blocks = !args.solve_with_trsm && !args.complete_inv && h1 > 0 && h1 < n;
+    const bool blocks = !subst && !args.solve_with_trsm && !args.complete_inv && h1 > 0 && h1 < n;
     if (args.X.filled() && args.X.num_columns_local() != r) args.X._destroy_();
     args.X._register_(r, n, 1, 1);
-    args.SolveW1._register_(W, n, 1, 1);
+    if (!subst) args.SolveW1._register_(W, n, 1, 1);
     if (blocks) args.SolveW2._register_(W, n, 1, 1);
     if (refine > 0) { args.SolveRho._register_(W, n, 1, 1); args.SolveD._register_(W, n, 1, 1); }
     const double* Rp = (const double*)args.R.data();
@@ -270,6 +279,12 @@ public:
     };
     // Xo (n x rb, ld n) <- A^-1 Bi; Bi is not written and Xo != Bi
     auto apply = [&](const double* Bi, double* Xo, int64_t rb) {
+      if (subst) {
+        CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));
+        CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_TRANS, n, rb, Rp, packed ? 0 : n, 0, Xo, n));             // y = R^-T b
+        CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_NOTRANS, n, rb, Rp, packed ? 0 : n, 0, Xo, n));           // x = R^-1 y
+        return;
+      }
       double* w1 = args.SolveW1.data();
       if (args.solve_with_trsm) {
         CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));

@@ -163,6 +163,17 @@ int capi_dresid_ts(capi_handle_t h, int64_t m, int64_t n, int64_t r, const doubl
  * the entries below the diagonal take part as zeros (0 * B(k)), so a NaN or Inf in B reaches output lines that it does not belong to. */
 int capi_dtrmm_thin(capi_handle_t h, int shape, int trans, int64_t m, int64_t n, int64_t r, double alpha,
                     const double* T, int64_t ldt, int64_t col0, const double* B, int64_t ldb, double beta, double* C, int64_t ldc);
+/* capi_dtrsm_thin: B (n x r, ldb >= n) <- op(T)^-1 B in place, by SUBSTITUTION, for the upper triangular T of order n with a non-unit diagonal: solves
+ * on the cholinv factor R itself (cholesky::cholinv::solve with info::solve_by_substitution).  Not in the reference: cholinv.hpp stops at R and R^-1.
+ * ldt >= n: column-major.  ldt == 0: a diagonal sub-triangle of a PACKED upper triangle that starts at the triangle's column col0, addressed as
+ * capi_dtrmm_thin addresses it (T points at the sub-triangle's first element; offsets are 64-bit).  1 <= r <= CAPI_TS_MAX_RHS (more: CAPI_EINVAL,
+ * nothing is touched); n == 0 is OK; pointers aligned to 8 bytes, any ldb.  No inverse of T or of a diagonal block is formed (reciprocals of
+ * diagonal entries only): LAPACK's row-wise backward stability.  Nothing below T's diagonal is read or influences the result.  No singularity check:
+ * a zero on the diagonal gives Inf or NaN as cblas_dtrsm does, and the info word is untouched.  T is read from HBM once per call: the triangle is
+ * cut into leaves of order <= 512, each substituted by one workgroup, and rectangular products through capi_dtrmm_thin (csrc/trsm_thin_plan.h);
+ * the steps are ordered by kernel boundaries on the handle's stream, sums have a fixed order (bit-identical runs, no atomics).
+ * Workspace: capi_dtrmm_thin's for the largest product, the top level's T12 (about n / 2 output lines), of the handle's workspace; none for n <= 512. */
+int capi_dtrsm_thin(capi_handle_t h, int trans, int64_t n, int64_t r, const double* T, int64_t ldt, int64_t col0, double* B, int64_t ldb);
 /* capi_dresid_sym: Rout (n x r) <- B - S X and colnorm2[j] <- sum_i Rout(i, j)^2 (DEVICE, r doubles) for the SYMMETRIC S whose upper triangle, diagonal
  * included, is that of the column-major A (lda >= n): the residual of cholesky::cholinv::solve.  Not in the reference: cholinv.hpp stops at R and R^-1.
  * NO element below A's diagonal influences any output: it may hold NaN, Inf or garbage (inside the tiles that the diagonal crosses the unwanted

@@ -14,11 +14,19 @@ pass of solve, Rout <- B - S X with its norms on a symmetric S, by three routes 
   (c) two capi_dtrmm_thin(CAPI_UPPERTRI) calls on full storage, NOTRANS and TRANS, and a diagonal correction (two elementwise device kernels;
       no norms): the triangle read twice, with no kernel of its own
 
-With --e2e N one Cholinv.solve
+With --subst ORDERS the solve by SUBSTITUTION
+on the factor itself (a synthetic, well-conditioned triangle), alternating:
+
+  (a) capi_dtrsm_thin, NOTRANS and TRANS, packed and full storage (run once per LEAF candidate of trsm_thin_plan.h: CAPITAL_HIP_LIB names the build)
+  (b) capi_dtrsm on full storage for the same r columns: what the TRSM-mode solve runs without info::solve_by_substitution
+  (c) capi_dtrmm_thin(CAPI_UPPERTRI) on a packed triangle (the inverse mode's product with R^-1) and the copy of the triangle's bytes
+
+and with --subst-e2e N Cholinv.solve with refine = 0 and 1, substitution off and on, in both factor modes (Serialize + SaveIntermediates: the only
+packed configuration in which the TRSM mode solves with the flag off).  With --e2e N one Cholinv.solve
 (config 2's policies: complete_inv = 0, split = 1, Serialize) beside its factor().  The parent process makes no GPU call: every order runs in a
 child of its own under a time limit, and a failed child ends the run.
 
-    python tools/solve_bench.py [--reps 9] [--orders 16384,32768] [--resid 16384,32768] [--e2e 32768] [--limit 300]"""
+    python tools/solve_bench.py [--reps 9] [--orders 16384,32768] [--resid 16384,32768] [--subst 32768] [--subst-e2e 32768] [--e2e 32768] [--limit 300]"""
 import argparse
 import os
 import statistics
@@ -179,6 +187,105 @@ def resid_child(n, reps, warmup):
     h.close()
 
 
+def subst_child(n, reps, warmup):
+    import ctypes as C
+    import torch
+    from capital_amd import capi
+    h = capi.Handle(0)
+    dev = "cuda:0"
+    g = torch.Generator(device=dev).manual_seed(3)
+    p = capi.ptr
+    # a well-conditioned upper triangle: unit diagonal, entries of size 1 / n above it (row j of the tensor is column j of the matrix)
+    Tf = torch.empty((n, n), dtype=torch.float64, device=dev)
+    for j0 in range(0, n, 4096):
+        blk = torch.randn((min(4096, n - j0), n), dtype=torch.float64, device=dev, generator=g) * (1.0 / n)
+        Tf[j0:j0 + blk.shape[0]] = torch.tril(blk, diagonal=j0 - 1)
+    torch.diagonal(Tf).fill_(1.0)
+    np_ = n * (n + 1) // 2
+    Tp = torch.empty(np_, dtype=torch.float64, device=dev)
+    h.call("capi_serialize", capi.RECT, capi.UPPERTRI, p(Tf), n, n, p(Tp), n, n, 0, n, 0, n, 0, n, 0, n)
+    h.sync()
+    ms = C.c_float()
+
+    def timed(fn):
+        h.call("capi_timer_start")
+        fn()
+        h.call("capi_timer_stop_ms", C.byref(ms))
+        return ms.value
+
+    print(f"== solve by substitution, n = {n}: the triangle is {8 * np_ / 1e9:.2f} GB packed; {reps} alternating rounds after {warmup} warm-up rounds; "
+          f"capi version {h.L.capi_version()}, library {os.path.basename(capi.LIB_PATH)}", flush=True)
+    for r in (1, 8, 32):
+        B0 = torch.randn((r, n), dtype=torch.float64, device=dev, generator=g)
+        X, Xb, Cm = torch.empty_like(B0), torch.empty_like(B0), capi.zeros(n, r)
+        csrc = torch.empty(np_ // 2, dtype=torch.float64, device=dev).normal_()
+        cdst = torch.empty_like(csrc)
+        steps = {}
+        for tn, t in (("N", capi.NOTRANS), ("T", capi.TRANS)):
+            steps[f"a.dtrsm_thin_{tn}.packed"] = lambda t=t: h.call("capi_dtrsm_thin", t, n, r, p(Tp), 0, 0, p(X), n)
+            steps[f"a.dtrsm_thin_{tn}.full"] = lambda t=t: h.call("capi_dtrsm_thin", t, n, r, p(Tf), n, 0, p(X), n)
+            steps[f"b.dtrsm_{tn}.full"] = lambda t=t: h.call("capi_dtrsm", capi.LEFT, capi.UPPER, t, capi.NONUNIT, n, r, 1.0, p(Tf), n, p(Xb), n)
+            steps[f"c.dtrmm_thin_{tn}.packed"] = lambda t=t: h.call("capi_dtrmm_thin", capi.UPPERTRI, t, n, n, r, 1.0, p(Tp), 0, 0, p(B0), n, 0.0, p(Cm), n)
+        steps["copy"] = lambda: cdst.copy_(csrc)
+        times = {k: [] for k in steps}
+        for i in range(warmup + reps):
+            for k, fn in steps.items():
+                X.copy_(B0)                                               # the solves are in place: every one starts from the same right-hand side
+                Xb.copy_(B0)
+                tm = timed(fn)
+                if i >= warmup:
+                    times[k].append(tm)
+        # the two routes compute the same thing: once more, TRANS, the thin solve on the packed and the block TRSM on the full operand
+        X.copy_(B0)
+        h.call("capi_dtrsm_thin", capi.TRANS, n, r, p(Tp), 0, 0, p(X), n)
+        Xb.copy_(B0)
+        h.call("capi_dtrsm", capi.LEFT, capi.UPPER, capi.TRANS, capi.NONUNIT, n, r, 1.0, p(Tf), n, p(Xb), n)
+        h.sync()
+        d = (X - Xb).abs().max().item() / max(Xb.abs().max().item(), 1e-300)
+        print(f"-- r = {r}:  max |X_a - X_b| / max |X_b| = {d:.2e}")
+        med = {k: statistics.median(v) for k, v in times.items()}
+        for k in steps:
+            extra = ""
+            if k.startswith("a."):
+                b = "b.dtrsm_" + k.split("_")[2].split(".")[0] + ".full"
+                extra = f"   (b) / (a) = {med[b] / med[k]:.2f}   min (b) / max (a) = {min(times[b]) / max(times[k]):.2f}   (a) / copy = {med[k] / med['copy']:.2f}"
+            print(f"   {k:26s} {statistics.median(times[k]):8.3f} ms [{min(times[k]):.3f} .. {max(times[k]):.3f}]{extra}")
+        print(f"   the copy moves {8 * np_ / 1e9:.2f} GB: {8 * np_ / med['copy'] / 1e9:.2f} TB/s at its median; the chain of {n} rows costs "
+              f"{min(med[k] for k in med if k.startswith('a.')) * 1e6 / n:.0f} ns per row at the fastest (a)", flush=True)
+        del B0, X, Xb, Cm, csrc, cdst
+    h.close()
+
+
+def subst_e2e(n):
+    import numpy as np
+    from capital_amd import driver
+    driver.init(0, 0, 1, None, use_torch_stream=False)
+    try:
+        rng = np.random.default_rng(0)
+        print(f"== Cholinv.solve, n = {n}, Serialize + SaveIntermediates, complete_inv = 0: best of 3, wall clock incl. the host copies of B and X")
+        for trsm in (False, True):
+            pr = driver.Cholinv(n, c=1, complete_inv=0, split=1, bc_mult=0 if n <= 2048 else -(max(n // 2048, 2).bit_length() - 1), trsm_mode=trsm)
+            pr.generate()
+            pr.factor()
+            for r in (1, 8, 32):
+                B = np.asfortranarray(rng.standard_normal((n, r)))
+                for refine in (0, 1):
+                    row = []
+                    for on in (False, True):
+                        pr.set_solve_substitution(on)
+                        v = []
+                        for _ in range(3):
+                            t0 = time.perf_counter()
+                            X, res = pr.solve(B, refine=refine, residual=True)
+                            v.append((time.perf_counter() - t0) * 1e3)
+                        row.append((min(v), float(res.max())))
+                    print(f"   {'TRSM' if trsm else 'inverse'} mode r = {r:2d} refine = {refine}: substitution off {row[0][0]:8.1f} ms (max ||b - A x|| = {row[0][1]:.2e}), "
+                          f"on {row[1][0]:8.1f} ms ({row[1][1]:.2e})", flush=True)
+            pr.close()
+    finally:
+        driver.finalize()
+
+
 def e2e(n):
     import numpy as np
     from capital_amd import driver
@@ -217,19 +324,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--orders", default="16384,32768")
     ap.add_argument("--resid", default="", help="orders of the residual pass: capi_dresid_sym against capi_dresid_ts and two capi_dtrmm_thin calls")
+    ap.add_argument("--subst", default="", help="orders of the solve by substitution: capi_dtrsm_thin against capi_dtrsm, capi_dtrmm_thin and the copy")
+    ap.add_argument("--subst-e2e", type=int, default=0, help="order of Cholinv.solve with substitution off and on, in both factor modes (0: none)")
     ap.add_argument("--e2e", type=int, default=0, help="order of one end-to-end factor() + solve (0: none)")
     ap.add_argument("--limit", type=int, default=300, help="seconds per child")
     ap.add_argument("--child", default=None)
     a = ap.parse_args()
     if a.child:
-        if a.child.startswith("e2e:"):
+        if a.child.startswith("subst_e2e:"):
+            subst_e2e(int(a.child[10:]))
+        elif a.child.startswith("subst:"):
+            subst_child(int(a.child[6:]), a.reps, a.warmup)
+        elif a.child.startswith("e2e:"):
             e2e(int(a.child[4:]))
         elif a.child.startswith("resid:"):
             resid_child(int(a.child[6:]), a.reps, a.warmup)
         else:
             child(int(a.child), a.reps, a.warmup)
         return 0
-    jobs = [o for o in a.orders.split(",") if o] + [f"resid:{o}" for o in a.resid.split(",") if o] + ([f"e2e:{a.e2e}"] if a.e2e else [])
+    jobs = [o for o in a.orders.split(",") if o] + [f"resid:{o}" for o in a.resid.split(",") if o] + [f"subst:{o}" for o in a.subst.split(",") if o]
+    jobs += ([f"subst_e2e:{a.subst_e2e}"] if a.subst_e2e else []) + ([f"e2e:{a.e2e}"] if a.e2e else [])
     for job in jobs:
         try:
             rc = subprocess.run([sys.executable, "-u", os.path.abspath(__file__), "--child", job, "--reps", str(a.reps), "--warmup", str(a.warmup)],
