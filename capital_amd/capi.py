@@ -42,6 +42,10 @@ _SIGS = {
     "capi_dtrmm_thin": [_int, _int, _i64, _i64, _i64, _dbl, _vp, _i64, _i64, _vp, _i64, _dbl, _vp, _i64],
     "capi_dtrsm_thin": [_int, _i64, _i64, _vp, _i64, _i64, _vp, _i64],
     "capi_dresid_sym": [_i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
+    "capi_dsym_abs": [_i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
+    "capi_dberr": [_i64, _i64, _vp, _i64, _vp, _i64, _vp],
+    "capi_dcolamax": [_i64, _i64, _vp, _i64, _vp],
+    "capi_dlacn_block": [_int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, C.POINTER(_int)],
     "capi_get_info": [C.POINTER(_int)],
     "capi_reset_info": [],
     "capi_serialize": [_int, _int, _vp, _i64, _i64, _vp, _i64, _i64] + [_i64] * 8,
@@ -139,6 +143,8 @@ def load():
     L.capi_pairs_scratch_count.argtypes = [_int, _i64]
     L.capi_pairs_scratch_count.restype = _i64
     L.capi_device_count.restype = _int
+    L.capi_dlacn_state_bytes.argtypes = [_i64, _i64]
+    L.capi_dlacn_state_bytes.restype = C.c_size_t
     _lib = L
     return L
 
@@ -148,7 +154,7 @@ def declared_symbols():
     import re
     hdr = os.path.join(os.path.dirname(_HERE), "include", "capital_hip.h")
     txt = open(hdr).read()
-    return sorted(set(re.findall(r"^(?:int|int64_t|void\*|const char\*)\s+(capi_[a-z0-9_]+)\s*\(", txt, re.M)))
+    return sorted(set(re.findall(r"^(?:int|int64_t|size_t|void\*|const char\*)\s+(capi_[a-z0-9_]+)\s*\(", txt, re.M)))
 
 
 def ptr(t):

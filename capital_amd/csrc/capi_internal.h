@@ -67,7 +67,7 @@ struct capi_handle_s {
 
 enum { CAPI_ATTR_LEAF = 0, CAPI_ATTR_TRMM_TS32 = 1, CAPI_ATTR_GRAM_TS = 3, CAPI_ATTR_SMALL0 = 4 /* ..7 */,
        CAPI_ATTR_GRAM_WIDE = 8, CAPI_ATTR_TRMM_WIDE = 9, CAPI_ATTR_PAIR0 = 10 /* ..13 */, CAPI_ATTR_RESID_TS0 = 14 /* ..15 */, CAPI_ATTR_TRMM_THIN0 = 16 /* ..19 */,
-       CAPI_ATTR_RESID_SYM = 20, CAPI_ATTR_TRSM_THIN0 = 21 /* ..26 */ };
+       CAPI_ATTR_RESID_SYM = 20, CAPI_ATTR_TRSM_THIN0 = 21 /* ..26 */, CAPI_ATTR_SYM_ABS = 27 };
 #define CAPI_RAISE_LDS_LIMIT(h, bit, fn, bytes)                                                                    \
   do {                                                                                                             \
     if (!((h)->lds_attr_done & (1u << (bit)))) {                                                                   \

@@ -1,7 +1,8 @@
 // sym_apply_f64.hip -- a SYMMETRIC matrix, given by its upper triangle, times a thin block (r <= 32 columns): the residual of the solves on the
-// cholinv factors (cholesky::cholinv::solve).  Not in the reference: its cholinv stops at R and R^-1.
+// cholinv factors (cholesky::cholinv::solve) and the weights of their error bounds.  Not in the reference: its cholinv stops at R and R^-1.
 //
 //   capi_dresid_sym   Rout (n x r) <- B - S X, colnorm2[j] <- sum_i Rout(i, j)^2      S = triu(A) + triu(A, 1)^T, column-major A
+//   capi_dsym_abs     W (n x r) <- |S| |X| + |B|, colmax[j] <- max_i W(i, j)          the same kernel on absolute values, at every r (16 columns a pass)
 //
 // The upper triangle is read from HBM once; nothing below A's diagonal is read into a result.  The triangle is cut into a p x p block triangle,
 // one workgroup per block (sym_thin_plan.h).  A 32 x 32 tile U of block (I, J) feeds two products: U X_J goes to the lines of I and U^T X_I to
@@ -45,6 +46,9 @@ struct SymArgs {
   sp::Plan P;
 };
 
+// ABS: |U| |X| instead of U X (capi_dsym_abs): the thin operand loses its signs on the way into LDS, a tile's pieces just before they are multiplied.
+// The ABS == false instantiation is the kernel as it was, instruction for instruction
+template <bool ABS>
 __global__ __launch_bounds__(SY_THREADS) void resid_sym_kernel(const SymArgs p) {
   extern __shared__ __attribute__((aligned(16))) double Ls[];   // [4][256][16]: X_J(k, j), X_I(k, j) twice, (U^T X_I)(col, j)
   double* const XJ = Ls;
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(SY_THREADS) void resid_sym_kernel(const SymArgs p) 
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int j = fj + 2 * q;
-      L[fk * 16 + j] = (k < n && j < p.r) ? xst[q] : 0.0;
+      L[fk * 16 + j] = (k < n && j < p.r) ? (ABS ? fabs(xst[q]) : xst[q]) : 0.0;
     }
   };
 
@@ -152,6 +156,11 @@ __global__ __launch_bounds__(SY_THREADS) void resid_sym_kernel(const SymArgs p) 
     const int c = (w + t) & 7;
     if (live(C, R, t)) {
       d4_t acc2[2][1] = {{(d4_t){0.0, 0.0, 0.0, 0.0}}, {(d4_t){0.0, 0.0, 0.0, 0.0}}};   // (U^T X_I)(col0 + 16 s + g4 + 4 reg, l16)
+      if constexpr (ABS) {
+        // here, not where the pieces are loaded: the prefetched set must stay in flight over the step before
+#pragma unroll
+        for (int q = 0; q < SY_NP; ++q) { na[q] = __builtin_elementwise_abs(na[q]); ta[q] = __builtin_elementwise_abs(ta[q]); }
+      }
       __builtin_amdgcn_s_setprio(1);
       tt::mfma_row_dots<1>(acc1, XJ + (32 * c + g4) * 16 + l16, 0, na);
       tt::mfma_col_dots<1>(acc2, XI + par * SY_IMG + (32 * w + 2 * g4) * 16 + l16, 0, ta);
@@ -237,6 +246,29 @@ __global__ __launch_bounds__(sp::SUPER) void resid_sym_combine_kernel(const SymC
   });
 }
 
+struct SymAbsCombineArgs {
+  const double* slab; const double* B; double* W; double* part;
+  int64_t ldb, ldw;
+  int r;
+  sp::Plan P;
+};
+
+// capi_dsym_abs: W(l, j) = (the p + 1 slots of l's line block, in the plan's order) + |B(l, j)|; part[group][j] = the largest over the group's 256 lines
+__global__ __launch_bounds__(sp::SUPER) void sym_abs_combine_kernel(const SymAbsCombineArgs p) {
+  const int64_t l = (int64_t)blockIdx.x * sp::SUPER + threadIdx.x;
+  const bool in = l < p.P.n;
+  const int L = in ? (int)(l / p.P.bs) : 0;
+  const int64_t x = in ? l - (int64_t)L * p.P.bs : 0, sd = sp::slot_doubles(p.P);
+  tt::group_colmax<sp::RPAD, sp::SUPER>(p.r, p.part, (int)CAPI_TS_MAX_RHS, [&](int j) {
+    if (!in) return 0.0;
+    double sum = 0.0;
+    for (int k = 0; k <= p.P.p; ++k) sum += p.slab[(int64_t)sp::contribution(p.P, L, k) * sd + (int64_t)j * p.P.bs + x];
+    const double v = p.B ? sum + fabs(p.B[l + (int64_t)j * p.ldb]) : sum;
+    if (p.W) p.W[l + (int64_t)j * p.ldw] = v;
+    return v;
+  });
+}
+
 // the two-pass route's last step: W = U X + U^T X counted the diagonal twice.  Rout(l, j) = B(l, j) - (W(l, j) - A(l, l) X(l, j)); part as above,
 // CAPI_TS_MAX_RHS columns per group
 __global__ __launch_bounds__(sp::SUPER) void resid_sym_finish_kernel(const double* __restrict__ W, const double* __restrict__ A, int64_t lda,
@@ -298,18 +330,57 @@ int capi_dresid_sym(capi_handle_t h, int64_t n, int64_t r, const double* A, int6
   if (rc != CAPI_OK) return rc;
   double* slab = (double*)pv;
   double* part = slab + sp::slab_doubles(P);
-  CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_RESID_SYM, resid_sym_kernel, SY_LDS);
+  CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_RESID_SYM, resid_sym_kernel<false>, SY_LDS);
   SymArgs p;
   p.A = A; p.X = X; p.slab = slab;
   p.lda = lda; p.ldx = ldx;
   p.r = (int)r; p.P = P;
-  hipLaunchKernelGGL(resid_sym_kernel, dim3((unsigned)sp::num_blocks(P)), dim3(SY_THREADS), SY_LDS, h->stream, p);
+  hipLaunchKernelGGL(resid_sym_kernel<false>, dim3((unsigned)sp::num_blocks(P)), dim3(SY_THREADS), SY_LDS, h->stream, p);
   SymCombineArgs cp;
   cp.slab = slab; cp.B = B; cp.R = Rout; cp.part = colnorm2 ? part : nullptr;
   cp.ldb = ldb; cp.ldr = ldr;
   cp.r = (int)r; cp.P = P;
   hipLaunchKernelGGL(resid_sym_combine_kernel, dim3((unsigned)groups), dim3(sp::SUPER), 0, h->stream, cp);
   if (colnorm2) hipLaunchKernelGGL(tt::colnorms_kernel<>, dim3(1), dim3(64), 0, h->stream, (const double*)part, groups, sp::RPAD, (int)r, colnorm2);
+  CAPI_HIP_CHECK(h, hipGetLastError());
+  return CAPI_OK;
+}
+
+int capi_dsym_abs(capi_handle_t h, int64_t n, int64_t r, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B, int64_t ldb,
+                  double* W, int64_t ldw, double* colmax) {
+  CAPI_REQUIRE(h, h, "null handle");
+  CAPI_REQUIRE_THIN_R(h, r);
+  CAPI_REQUIRE(h, n >= 0 && n < (1LL << 31) && lda < (1LL << 24), "n / lda (lda < 2^24: 32 columns are addressed by 32-bit byte offsets)");
+  CAPI_REQUIRE(h, n == 0 || (A && X && lda >= n && ldx >= n && (!B || ldb >= n) && (!W || ldw >= n)), "A/lda/X/ldx/B/ldb/W/ldw");
+  CAPI_REQUIRE(h, !W || W != X, "W must not alias X");
+  const int64_t groups = cdiv(n, sp::SUPER);
+  if (n == 0) {
+    if (colmax) hipLaunchKernelGGL(tt::colmax_kernel<>, dim3(1), dim3(64), 0, h->stream, (const double*)nullptr, (int64_t)0, (int)CAPI_TS_MAX_RHS, (int)r, colmax);
+    CAPI_HIP_CHECK(h, hipGetLastError());
+    return CAPI_OK;
+  }
+  const sp::Plan P = sp::make_plan(n, capi_stream_cus(h));
+  void* pv = nullptr;
+  int rc = capi_ws_get(h, sizeof(double) * (size_t)(sp::slab_doubles(P) + groups * CAPI_TS_MAX_RHS), &pv);
+  if (rc != CAPI_OK) return rc;
+  double* slab = (double*)pv;
+  double* part = slab + sp::slab_doubles(P);
+  CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_SYM_ABS, resid_sym_kernel<true>, SY_LDS);
+  // the fused kernel holds 16 columns (sym_thin_plan::RPAD): the triangle is read once per pass, the slab is reused in stream order
+  for (int64_t j0 = 0; j0 < r; j0 += sp::RPAD) {
+    const int rp = (int)sp::min64(sp::RPAD, r - j0);
+    SymArgs p;
+    p.A = A; p.X = X + j0 * ldx; p.slab = slab;
+    p.lda = lda; p.ldx = ldx;
+    p.r = rp; p.P = P;
+    hipLaunchKernelGGL(resid_sym_kernel<true>, dim3((unsigned)sp::num_blocks(P)), dim3(SY_THREADS), SY_LDS, h->stream, p);
+    SymAbsCombineArgs cp;
+    cp.slab = slab; cp.B = B ? B + j0 * ldb : nullptr; cp.W = W ? W + j0 * ldw : nullptr; cp.part = colmax ? part + j0 : nullptr;
+    cp.ldb = ldb; cp.ldw = ldw;
+    cp.r = rp; cp.P = P;
+    hipLaunchKernelGGL(sym_abs_combine_kernel, dim3((unsigned)groups), dim3(sp::SUPER), 0, h->stream, cp);
+  }
+  if (colmax) hipLaunchKernelGGL(tt::colmax_kernel<>, dim3(1), dim3(64), 0, h->stream, (const double*)part, groups, (int)CAPI_TS_MAX_RHS, (int)r, colmax);
   CAPI_HIP_CHECK(h, hipGetLastError());
   return CAPI_OK;
 }

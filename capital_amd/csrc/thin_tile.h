@@ -70,6 +70,27 @@ __device__ __forceinline__ void group_colnorms(int r, double* part, int stride, 
   __syncthreads();
   if (part && tid < r) part[(int64_t)blockIdx.x * stride + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
 }
+// the larger of the two, a NaN winning over any number: a maximum that must not hide one
+__device__ __forceinline__ double max_nan(double m, double v) { return (v > m || v != v) ? v : m; }
+template <int LANES>
+__device__ __forceinline__ double butterfly_max(double v) {
+#pragma unroll
+  for (int d = 1; d < LANES; d <<= 1) v = max_nan(v, __shfl_xor(v, d));
+  return v;
+}
+// the column maxima in group_colnorms's arrangement: part[group blockIdx.x][j] = the largest value(j) of the workgroup's 256 lines (part may be null)
+template <int MAXR, int THREADS, class VALUE>
+__device__ __forceinline__ void group_colmax(int r, double* part, int stride, VALUE&& value) {
+  static_assert(THREADS == 256, "red[][4] is for four waves");
+  __shared__ double red[MAXR][4];
+  const int tid = threadIdx.x;
+  for (int j = 0; j < r; ++j) {
+    const double m = butterfly_max<64>(value(j));
+    if ((tid & 63) == 0) red[j][tid >> 6] = m;
+  }
+  __syncthreads();
+  if (part && tid < r) part[(int64_t)blockIdx.x * stride + tid] = max_nan(max_nan(max_nan(red[tid][0], red[tid][1]), red[tid][2]), red[tid][3]);
+}
 // colnorm2[j] = part[group 0][j] + part[group 1][j] + ..  (groups of `stride` doubles); groups == 0 gives zeros.  Local to the including file (the
 // anonymous namespace), and a template so that only the files that launch it hold a copy
 namespace {
@@ -80,6 +101,15 @@ __global__ __launch_bounds__(64) void colnorms_kernel(const double* __restrict__
   double sum = 0.0;
   for (int64_t g = 0; g < groups; ++g) sum += part[g * stride + j];
   colnorm2[j] = sum;
+}
+// colmax[j] = the largest of part[group][j] (values >= 0, or NaN); groups == 0 gives zeros
+template <class = void>
+__global__ __launch_bounds__(64) void colmax_kernel(const double* __restrict__ part, int64_t groups, int stride, int r, double* __restrict__ colmax) {
+  const int j = threadIdx.x;
+  if (j >= r) return;
+  double m = 0.0;
+  for (int64_t g = 0; g < groups; ++g) m = max_nan(m, part[g * stride + j]);
+  colmax[j] = m;
 }
 }  // namespace
 

@@ -56,6 +56,10 @@ def bind(D):
     D.capital_cholinv_set_trsm_mode.argtypes = [_vp, _int]
     D.capital_cholinv_set_solve_substitution.argtypes = [_vp, _int]
     D.capital_cholinv_solve.argtypes = [_vp, _i64, _dp, _dp, _dp, _int]
+    D.capital_cholinv_rcond.argtypes = [_vp, _dp, _dp]
+    D.capital_cholinv_rcond_applies.argtypes = [_vp, _dp, _dp, C.POINTER(_int)]
+    D.capital_cholinv_error_bounds.argtypes = [_vp, _i64, _dp, _dp, _dp]
+    D.capital_cholinv_solve_expert.argtypes = [_vp, _i64, _dp, _dp, _dp, _int, _dp, _dp]
     D.capital_cacqr_create.argtypes = [_i64, _i64] + [_int] * 8
     D.capital_cacqr_create.restype = _vp
     D.capital_cacqr_set_A.argtypes = [_vp, _dp]
@@ -192,6 +196,33 @@ class Cholinv:
         _ck(self.D.capital_cholinv_solve(self.p, r, b.ctypes.data_as(_dp), X.ctypes.data_as(_dp), res.ctypes.data_as(_dp) if residual else None,
                                          int(refine)), "solve")
         return X, res
+
+    def rcond(self, details=False):
+        """The reciprocal condition number 1 / (||A||_1 ||A^-1||_1) of the factored A as LAPACK's dpocon estimates it (cholesky::cholinv::condition,
+        one rank): ||A||_1 from one pass over A's upper triangle, ||A^-1||_1 by the Hager-Higham estimator over the operator of solve() -- at most 11
+        products with A^-1 on one column.  The estimate of ||A^-1||_1 is a lower bound, so rcond errs on the large side (rarely by more than 3).
+        0.0: singular to working precision (the estimate overflowed).  details=True returns (rcond, ||A||_1, products)."""
+        v, a, k = _dbl(), _dbl(), _int()
+        _ck(self.D.capital_cholinv_rcond_applies(self.p, C.byref(v), C.byref(a), C.byref(k)), "rcond")
+        return (v.value, a.value, k.value) if details else v.value
+
+    def solve_expert(self, B, refine=1, residual=True):
+        """solve(B, refine, residual), then dporfs's bounds for its X (cholesky::cholinv::error_bounds).  Returns (X, resnorms, ferr, berr):
+        berr[j] is the componentwise backward error of x_j (the smallest e with (A + dA) x_j = b_j + db_j, |dA| <= e |A|, |db_j| <= e |b_j|),
+        ferr[j] an estimated bound on ||x_j - x_true,j||_inf / ||x_j||_inf.  Per block of 32 columns the bounds cost three passes over A's upper
+        triangle and at most 11 products with A^-1 (an unrefined solve of the block each).  X and resnorms are solve()'s, bit for bit."""
+        b = np.asfortranarray(B, dtype=np.float64)
+        if b.ndim == 1:
+            b = np.asfortranarray(b[:, None])
+        if b.ndim != 2 or b.shape[0] != self.n or b.shape[1] < 1:
+            raise DriverError(f"Cholinv.solve_expert: B must be {self.n} x r with r >= 1, got {b.shape}")
+        r = b.shape[1]
+        X = np.zeros((self.n, r), order="F")
+        res = np.zeros(r) if residual else None
+        ferr, berr = np.zeros(r), np.zeros(r)
+        _ck(self.D.capital_cholinv_solve_expert(self.p, r, b.ctypes.data_as(_dp), X.ctypes.data_as(_dp), res.ctypes.data_as(_dp) if residual else None,
+                                                int(refine), ferr.ctypes.data_as(_dp), berr.ctypes.data_as(_dp)), "solve_expert")
+        return X, res, ferr, berr
 
     def _get(self, which):
         out = np.zeros((self.n_loc, self.n_loc), order="F")

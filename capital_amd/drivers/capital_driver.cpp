@@ -40,6 +40,8 @@ struct cholinv_problem {
   virtual void set_trsm_mode(bool on) = 0;
   virtual void set_solve_substitution(bool on) = 0;
   virtual void solve(int64_t r, const double* B_host, double* X_host, double* resnorm_host, int refine) = 0;
+  virtual void rcond(double* rcond, double* anorm1, int* applies) = 0;
+  virtual void error_bounds(int64_t r, const double* B_host, double* ferr_host, double* berr_host, int* applies) = 0;
 };
 
 template <class Alg>
@@ -89,6 +91,23 @@ struct cholinv_impl : cholinv_problem {
     auto x = pack.X.to_host();
     std::memcpy(X_host, x.data(), sizeof(double) * x.size());
     if (resnorm_host) std::memcpy(resnorm_host, pack.solve_residual_norms.data(), sizeof(double) * (size_t)r);
+  }
+  void rcond(double* rcond, double* anorm1, int* applies) override {
+    if (!rcond) throw std::invalid_argument("cholinv rcond: a place for the result expected");
+    Alg::condition(A, pack, grid);
+    *rcond = pack.rcond;
+    if (anorm1) *anorm1 = pack.anorm1;
+    if (applies) *applies = pack.lacn_applies;
+  }
+  // bounds for the X that the last solve left on the device, B_host the n x r right-hand sides of that solve
+  void error_bounds(int64_t r, const double* B_host, double* ferr_host, double* berr_host, int* applies) override {
+    if (r < 1 || !B_host || !ferr_host || !berr_host) throw std::invalid_argument("cholinv error_bounds: r >= 1 right-hand sides, B, ferr and berr expected");
+    MatrixType B(r, A.num_rows_global(), 1, 1);
+    B.from_host(B_host);
+    Alg::error_bounds(A, B, pack, grid);
+    std::memcpy(ferr_host, pack.solve_ferr.data(), sizeof(double) * (size_t)r);
+    std::memcpy(berr_host, pack.solve_berr.data(), sizeof(double) * (size_t)r);
+    if (applies) *applies = pack.lacn_applies;
   }
 };
 
@@ -244,6 +263,29 @@ int capital_cholinv_set_solve_substitution(void* p, int on) { return guarded([&]
 // Refinement and residual read A's upper triangle alone, as the factorization does: A need not be stored symmetric
 int capital_cholinv_solve(void* p, int64_t r, const double* B_host, double* X_host, double* resnorm_host_or_null, int refine) {
   return guarded([&] { ((cholinv_problem*)p)->solve(r, B_host, X_host, resnorm_host_or_null, refine); });
+}
+// How far to trust a solve (cholesky::cholinv::condition / error_bounds; one rank, after capital_cholinv_factor).
+// rcond: the reciprocal 1-norm condition number as LAPACK's dpocon estimates it; anorm1_or_null receives ||A||_1
+int capital_cholinv_rcond(void* p, double* rcond, double* anorm1_or_null) {
+  return guarded([&] { ((cholinv_problem*)p)->rcond(rcond, anorm1_or_null, nullptr); });
+}
+// the same with the number of products with A^-1 that the estimate took (at most 11)
+int capital_cholinv_rcond_applies(void* p, double* rcond, double* anorm1_or_null, int* applies_or_null) {
+  return guarded([&] { ((cholinv_problem*)p)->rcond(rcond, anorm1_or_null, applies_or_null); });
+}
+// dporfs's bounds for the X that the last capital_cholinv_solve[_expert] left on the device: B_host must be that solve's right-hand sides (r must
+// match the resident X).  ferr_host[j] bounds ||x_j - x_true,j||_inf / ||x_j||_inf, berr_host[j] is the componentwise backward error
+int capital_cholinv_error_bounds(void* p, int64_t r, const double* B_host, double* ferr_host, double* berr_host) {
+  return guarded([&] { ((cholinv_problem*)p)->error_bounds(r, B_host, ferr_host, berr_host, nullptr); });
+}
+// capital_cholinv_solve, then capital_cholinv_error_bounds on its X (LAPACK's dposvx without equilibration)
+int capital_cholinv_solve_expert(void* p, int64_t r, const double* B_host, double* X_host, double* resnorm_host_or_null, int refine, double* ferr_host,
+                                 double* berr_host) {
+  return guarded([&] {
+    if (!ferr_host || !berr_host) throw std::invalid_argument("cholinv solve_expert: ferr and berr expected");
+    ((cholinv_problem*)p)->solve(r, B_host, X_host, resnorm_host_or_null, refine);
+    ((cholinv_problem*)p)->error_bounds(r, B_host, ferr_host, berr_host, nullptr);
+  });
 }
 int capital_cholinv_destroy(void* p) { return guarded([&] { capital::sync(); delete (cholinv_problem*)p; }); }
 

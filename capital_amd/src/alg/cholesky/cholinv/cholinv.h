@@ -27,6 +27,12 @@
 #pragma weak capi_dresid_sym
 // .. and so is the thin triangular solve of info::solve_by_substitution: without it solve() runs as before and refuses only that flag
 #pragma weak capi_dtrsm_thin
+// .. and the pieces of condition() / error_bounds(): without them factor() and solve() run as before and those two refuse
+#pragma weak capi_dsym_abs
+#pragma weak capi_dberr
+#pragma weak capi_dcolamax
+#pragma weak capi_dlacn_block
+#pragma weak capi_dlacn_state_bytes
 
 namespace cholesky {
 
@@ -88,6 +94,13 @@ public:
     // the solution X (n x r) and, when asked for, ||b_j - A x_j||_2 per right-hand side; n x CAPI_TS_MAX_RHS work blocks
     matrix<ScalarType, DimensionType, rect> X, SolveW1, SolveW2, SolveRho, SolveD, SolveNorm2;
     std::vector<double> solve_residual_norms;
+    // condition(): ||A||_1, the reciprocal condition number 1 / (||A||_1 est ||A^-1||_1) as dpocon returns it, and the products with A^-1 that the
+    // estimate took (at most 11).  error_bounds(): per column of X the componentwise backward error and the forward bound of dporfs, and the
+    // products its slowest block of columns took.  The work blocks of both: n x CAPI_TS_MAX_RHS each, the estimator's state, a few small results
+    double anorm1 = 0.0, rcond = 0.0;
+    int lacn_applies = 0;
+    std::vector<double> solve_ferr, solve_berr;
+    matrix<ScalarType, DimensionType, rect> BoundsRho, BoundsWt, BoundsV1, BoundsV2, BoundsState, BoundsSmall;
   };
 
   template <typename MatrixType, typename ArgType, typename CommType>
@@ -239,72 +252,20 @@ public:
   template <typename MatrixType, typename ArgType, typename CommType>
   static void solve(const MatrixType& A, const MatrixType& B, ArgType& args, CommType&& CommInfo, int refine = 1, bool residual = true) {
     static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::solve takes rect-structured A and B");
-    constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
-    if (CommInfo.size > 1) throw std::logic_error("cholinv::solve is built for one rank: on a grid the factors are element-cyclic (factor there, solve on one rank)");
-    if (!&capi_dtrmm_thin || !&capi_dresid_ts) throw std::logic_error("cholinv: this C-ABI library has no capi_dtrmm_thin / capi_dresid_ts: no solve");
-    const bool subst = args.solve_by_substitution;
-    if (subst && !&capi_dtrsm_thin) throw std::logic_error("cholinv: this C-ABI library has no capi_dtrsm_thin: no solve by substitution");
-    if (!args.factored || args.potrf_info != 0 || !args.R.filled() || (!args.solve_with_trsm && !args.Rinv.filled()))
-      throw std::logic_error("cholinv::solve: factor() has not run or did not succeed: there are no valid factors to solve with");
-    if (args.factored_trsm != args.solve_with_trsm)
-      throw std::logic_error("cholinv::solve: solve_with_trsm was changed after factor(): the resident factors are those of the other mode; factor() again");
+    require_factors(args, CommInfo, "cholinv::solve");
     const int64_t n = args.localDimension, r = B.num_columns_global();
     if (r < 1 || B.num_rows_global() != n || B.num_rows_local() != n || A.num_rows_local() != n || A.num_columns_local() != n || refine < 0)
       throw std::invalid_argument("cholinv::solve: B must be n x r with r >= 1 (matrix(r, n, 1, 1)), A the factored matrix, refine >= 0");
-    const double* Rfullp = nullptr;
-    if (args.solve_with_trsm && !subst) {
-      // (FlushIntermediates promises that no full-storage working image outlives factor(): none is relied on there, whatever is still allocated)
-      Rfullp = packed ? (IP::keep_arena && args.Rfull.filled() ? args.Rfull.data() : nullptr) : (const double*)args.R.data();
-      if (!Rfullp)
-        throw std::logic_error("cholinv::solve: TRSM mode with Serialize + FlushIntermediates leaves only the packed R, and capi_dtrsm takes full "
-                               "storage: use SaveIntermediates or NoSerialize with solve_with_trsm");
-    }
+    const double* Rfullp = full_storage_R(args, "cholinv::solve");
     CRITTER_START(CI::solve);
     capi_handle_t h = capital::handle();
     CAPITAL_CHECK(capi_stream_select(h, 0));
-    const int64_t W = CAPI_TS_MAX_RHS, h1 = args.top_split;
-    const bool blocks = !subst && !args.solve_with_trsm && !args.complete_inv && h1 > 0 && h1 < n;
+    const int64_t W = CAPI_TS_MAX_RHS;
     if (args.X.filled() && args.X.num_columns_local() != r) args.X._destroy_();
     args.X._register_(r, n, 1, 1);
-    if (!subst) args.SolveW1._register_(W, n, 1, 1);
-    if (blocks) args.SolveW2._register_(W, n, 1, 1);
+    const applier ap = make_applier(args, Rfullp);
     if (refine > 0) { args.SolveRho._register_(W, n, 1, 1); args.SolveD._register_(W, n, 1, 1); }
-    const double* Rp = (const double*)args.R.data();
-    const double* Ip = args.solve_with_trsm ? nullptr : (const double*)args.Rinv.data();
-    // the block of a factor whose first element is (i0, j0): a view into the packed triangle (ldt == 0, col0 = j0) or into the rect structure
-    auto thin = [&](const double* F, int shape, int trans, int64_t i0, int64_t j0, int64_t m, int64_t k, int64_t rb, double alpha, const double* Bp,
-                    double beta, double* Cp) {
-      const double* Tp = packed ? F + j0 * (j0 + 1) / 2 + i0 : F + i0 + j0 * n;
-      CAPITAL_CHECK(capi_dtrmm_thin(h, shape, trans, m, k, rb, alpha, Tp, packed ? 0 : n, packed ? j0 : 0, Bp, n, beta, Cp, n));
-    };
-    // Xo (n x rb, ld n) <- A^-1 Bi; Bi is not written and Xo != Bi
-    auto apply = [&](const double* Bi, double* Xo, int64_t rb) {
-      if (subst) {
-        CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));
-        CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_TRANS, n, rb, Rp, packed ? 0 : n, 0, Xo, n));             // y = R^-T b
-        CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_NOTRANS, n, rb, Rp, packed ? 0 : n, 0, Xo, n));           // x = R^-1 y
-        return;
-      }
-      double* w1 = args.SolveW1.data();
-      if (args.solve_with_trsm) {
-        CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));
-        CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_TRANS, CAPI_NONUNIT, n, rb, 1.0, Rfullp, n, Xo, n));
-        CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, n, rb, 1.0, Rfullp, n, Xo, n));
-      } else if (!blocks) {
-        thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, 0, 0, n, n, rb, 1.0, Bi, 0.0, w1);
-        thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, 0, 0, n, n, rb, 1.0, w1, 0.0, Xo);
-      } else {
-        const int64_t h2 = n - h1;
-        double* w2 = args.SolveW2.data();
-        thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, 0, 0, h1, h1, rb, 1.0, Bi, 0.0, w1);                          // y1 = R11^-T b1
-        CAPITAL_CHECK(capi_dlacpy(h, 0, h2, rb, Bi + h1, n, w2 + h1, n));
-        thin(Rp, CAPI_RECT, CAPI_TRANS, 0, h1, h1, h2, rb, -1.0, w1, 1.0, w2 + h1);                      // b2 - R12^T y1
-        thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, h1, h1, h2, h2, rb, 1.0, w2 + h1, 0.0, w1 + h1);             // y2 = R22^-T (..)
-        thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, h1, h1, h2, h2, rb, 1.0, w1 + h1, 0.0, Xo + h1);           // x2 = R22^-1 y2
-        thin(Rp, CAPI_RECT, CAPI_NOTRANS, 0, h1, h1, h2, rb, -1.0, Xo + h1, 1.0, w1);                    // y1 - R12 x2
-        thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, 0, 0, h1, h1, rb, 1.0, w1, 0.0, Xo);                       // x1 = R11^-1 (..)
-      }
-    };
+    auto apply = [&](const double* Bi, double* Xo, int64_t rb) { apply_inverse(ap, Bi, Xo, rb); };
     // Ro (or nothing) <- Bi - A Xi, norm2 (or nothing) <- its squared column norms, from A's upper triangle
     auto resid = [&](int64_t rb, const double* Xi, const double* Bi, double* Ro, double* norm2) {
       if (&capi_dresid_sym) { CAPITAL_CHECK(capi_dresid_sym(h, n, rb, A.data(), n, Xi, n, Bi, n, Ro, Ro ? n : 0, norm2)); }
@@ -334,6 +295,95 @@ public:
       args.SolveW1._destroy_(); args.SolveW2._destroy_(); args.SolveRho._destroy_(); args.SolveD._destroy_();
     }
     CRITTER_STOP(CI::solve);
+  }
+
+  // How well A is conditioned, from the factors factor(A, args, CommInfo) left (LAPACK dpocon; ONE rank, solve()'s preconditions):
+  //   args.anorm1 = ||A||_1         one pass over A's upper triangle (capi_dsym_abs on a vector of ones)
+  //   args.rcond  = 1 / (anorm1 est), est <= ||A^-1||_1 by the Hager-Higham estimator (capi_dlacn_block) over the operator of solve(), whichever of
+  //                 its four forms the flags select: args.lacn_applies products with A^-1 on one column, at most 11; each costs what solve() pays for
+  //                 one unrefined right-hand side.  0 when the estimate is Inf or NaN (or anorm1 is 0); 1 for n == 0.
+  // The estimate is a lower bound of ||A^-1||_1 that is almost always within a factor 3 of it, so rcond errs on the large side.  Nothing of
+  // args.X is touched.  Memory: the estimator's two n x CAPI_TS_MAX_RHS blocks and its state, beside solve()'s own work blocks.
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void condition(const MatrixType& A, ArgType& args, CommType&& CommInfo) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::condition takes a rect-structured A");
+    require_factors(args, CommInfo, "cholinv::condition");
+    require_bounds_abi();
+    const int64_t n = args.localDimension;
+    if (A.num_rows_local() != n || A.num_columns_local() != n) throw std::invalid_argument("cholinv::condition: A must be the factored matrix");
+    const double* Rfullp = full_storage_R(args, "cholinv::condition");
+    args.anorm1 = 0.0; args.rcond = 1.0; args.lacn_applies = 0;
+    if (n == 0) return;
+    CRITTER_START(CI::condition);
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    const applier ap = make_applier(args, Rfullp);
+    register_bounds_work(args, false);
+    double* small = args.BoundsSmall.data();
+    {
+      const std::vector<double> ones((size_t)n, 1.0);
+      CAPITAL_CHECK(capi_memcpy_h2d(h, args.BoundsV1.data(), ones.data(), sizeof(double) * (size_t)n));
+    }
+    CAPITAL_CHECK(capi_dsym_abs(h, n, 1, A.data(), n, args.BoundsV1.data(), n, nullptr, 0, nullptr, 0, small));
+    args.lacn_applies = estimate(args, ap, 1, nullptr, small + 1);
+    double out[2];
+    CAPITAL_CHECK(capi_memcpy_d2h(h, out, small, sizeof(out)));
+    args.anorm1 = out[0];
+    const double prod = out[0] * out[1];
+    args.rcond = (std::isfinite(out[1]) && std::isfinite(prod) && prod > 0.0) ? 1.0 / prod : 0.0;
+    release_bounds_work(args);
+    CRITTER_STOP(CI::condition);
+  }
+
+  // How far the X of the last solve(A, B, ..) can be trusted (LAPACK dporfs without its refinement loop; ONE rank, solve()'s preconditions; B is the
+  // B of that solve, args.X is read and never written).  CAPI_TS_MAX_RHS columns at a time:
+  //   rho = B - A X (capi_dresid_sym), W = |A| |X| + |B| (capi_dsym_abs): two passes over A's upper triangle, plus one for more than 16 columns
+  //   args.solve_berr[j] = max_i |rho_ij| / W_ij: the componentwise backward error of x_j -- the smallest e with (A + dA) x_j = b_j + db_j,
+  //                        |dA| <= e |A|, |db_j| <= e |b_j| (capi_dberr, with dporfs's guard for tiny W_ij)
+  //   args.solve_ferr[j] >= (estimated) || |A^-1| (|rho_j| + (n + 1) u W_j) ||_inf / ||x_j||_inf, which bounds ||x_j - x_true,j||_inf / ||x_j||_inf:
+  //                        capi_dlacn_block runs the block's columns in lockstep over the operator of solve(), so 32 bounds cost the products of
+  //                        the slowest column (args.lacn_applies, at most 11; each costs what solve() pays for an unrefined block)
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void error_bounds(const MatrixType& A, const MatrixType& B, ArgType& args, CommType&& CommInfo) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::error_bounds takes rect-structured A and B");
+    require_factors(args, CommInfo, "cholinv::error_bounds");
+    require_bounds_abi();
+    const int64_t n = args.localDimension, r = B.num_columns_global();
+    if (r < 1 || B.num_rows_global() != n || B.num_rows_local() != n || A.num_rows_local() != n || A.num_columns_local() != n)
+      throw std::invalid_argument("cholinv::error_bounds: B must be n x r with r >= 1 (matrix(r, n, 1, 1)), A the factored matrix");
+    if (!args.X.filled() || args.X.num_columns_local() != r || args.X.num_rows_local() != n)
+      throw std::invalid_argument("cholinv::error_bounds: the resident X is not that of a solve with this B (no solve yet, or another number of columns)");
+    const double* Rfullp = full_storage_R(args, "cholinv::error_bounds");
+    args.solve_ferr.assign((size_t)r, 0.0);
+    args.solve_berr.assign((size_t)r, 0.0);
+    args.lacn_applies = 0;
+    if (n == 0) return;
+    CRITTER_START(CI::error_bounds);
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    const int64_t W = CAPI_TS_MAX_RHS;
+    const applier ap = make_applier(args, Rfullp);
+    register_bounds_work(args, true);
+    double *small = args.BoundsSmall.data(), *rho = args.BoundsRho.data(), *wt = args.BoundsWt.data();
+    for (int64_t j = 0; j < r; j += W) {
+      const int64_t rb = std::min(W, r - j);
+      const double* Xj = args.X.data() + j * n;
+      const double* Bj = B.data() + j * n;
+      CAPITAL_CHECK(capi_dresid_sym(h, n, rb, A.data(), n, Xj, n, Bj, n, rho, n, nullptr));
+      CAPITAL_CHECK(capi_dsym_abs(h, n, rb, A.data(), n, Xj, n, Bj, n, wt, n, nullptr));
+      CAPITAL_CHECK(capi_dberr(h, n, rb, rho, n, wt, n, small));                               // berr; wt becomes the forward bound's weights
+      CAPITAL_CHECK(capi_dcolamax(h, n, rb, Xj, n, small + 2 * W));                            // ||x_j||_inf
+      args.lacn_applies = std::max(args.lacn_applies, estimate(args, ap, rb, wt, small + W));
+      double out[3 * CAPI_TS_MAX_RHS];
+      CAPITAL_CHECK(capi_memcpy_d2h(h, out, small, sizeof(out)));
+      for (int64_t k = 0; k < rb; ++k) {
+        args.solve_berr[(size_t)(j + k)] = out[k];
+        const double est = out[W + k], xmax = out[2 * W + k];
+        args.solve_ferr[(size_t)(j + k)] = xmax > 0.0 ? est / xmax : est;                      // (dporfs: divided where the norm is positive)
+      }
+    }
+    release_bounds_work(args);
+    CRITTER_STOP(CI::error_bounds);
   }
 
   // ---- TRSM mode -----------------------------------------------------------------------------------------------------------
@@ -500,6 +550,130 @@ public:
   }
 
 private:
+  // ---- what solve(), condition() and error_bounds() share: the resident factors seen as the operator A^-1 on a thin block ----
+  struct applier {
+    capi_handle_t h;
+    int64_t n, h1;
+    bool subst, trsm, blocks;
+    const double *Rp, *Ip, *Rfullp;
+    double *w1, *w2;
+  };
+  // the full-storage R that capi_dtrsm needs (TRSM mode without substitution), or null where no form of the solve reads one
+  template <typename ArgType>
+  static const double* full_storage_R(ArgType& args, const char* who) {
+    constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
+    if (!(args.solve_with_trsm && !args.solve_by_substitution)) return nullptr;
+    // (FlushIntermediates promises that no full-storage working image outlives factor(): none is relied on there, whatever is still allocated)
+    const double* Rfullp = packed ? (IP::keep_arena && args.Rfull.filled() ? args.Rfull.data() : nullptr) : (const double*)args.R.data();
+    if (!Rfullp)
+      throw std::logic_error(std::string(who) + ": TRSM mode with Serialize + FlushIntermediates leaves only the packed R, and capi_dtrsm takes full "
+                             "storage: use SaveIntermediates or NoSerialize with solve_with_trsm");
+    return Rfullp;
+  }
+  // registers the work blocks of the form that the flags select
+  template <typename ArgType>
+  static applier make_applier(ArgType& args, const double* Rfullp) {
+    const int64_t W = CAPI_TS_MAX_RHS, n = args.localDimension, h1 = args.top_split;
+    applier c;
+    c.h = capital::handle();
+    c.n = n; c.h1 = h1;
+    c.subst = args.solve_by_substitution; c.trsm = args.solve_with_trsm;
+    c.blocks = !c.subst && !c.trsm && !args.complete_inv && h1 > 0 && h1 < n;
+    if (!c.subst) args.SolveW1._register_(W, n, 1, 1);
+    if (c.blocks) args.SolveW2._register_(W, n, 1, 1);
+    c.Rp = (const double*)args.R.data();
+    c.Ip = c.trsm ? nullptr : (const double*)args.Rinv.data();
+    c.Rfullp = Rfullp;
+    c.w1 = c.subst ? nullptr : args.SolveW1.data();
+    c.w2 = c.blocks ? args.SolveW2.data() : nullptr;
+    return c;
+  }
+  // Xo (n x rb, ld n) <- A^-1 Bi; Bi is not written and Xo != Bi
+  static void apply_inverse(const applier& c, const double* Bi, double* Xo, int64_t rb) {
+    constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
+    capi_handle_t h = c.h;
+    const int64_t n = c.n, h1 = c.h1;
+    const double *Rp = c.Rp, *Ip = c.Ip;
+    // the block of a factor whose first element is (i0, j0): a view into the packed triangle (ldt == 0, col0 = j0) or into the rect structure
+    auto thin = [&](const double* F, int shape, int trans, int64_t i0, int64_t j0, int64_t m, int64_t k, int64_t rb, double alpha, const double* Bp,
+                    double beta, double* Cp) {
+      const double* Tp = packed ? F + j0 * (j0 + 1) / 2 + i0 : F + i0 + j0 * n;
+      CAPITAL_CHECK(capi_dtrmm_thin(h, shape, trans, m, k, rb, alpha, Tp, packed ? 0 : n, packed ? j0 : 0, Bp, n, beta, Cp, n));
+    };
+    if (c.subst) {
+      CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));
+      CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_TRANS, n, rb, Rp, packed ? 0 : n, 0, Xo, n));             // y = R^-T b
+      CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_NOTRANS, n, rb, Rp, packed ? 0 : n, 0, Xo, n));           // x = R^-1 y
+      return;
+    }
+    double* w1 = c.w1;
+    if (c.trsm) {
+      CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));
+      CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_TRANS, CAPI_NONUNIT, n, rb, 1.0, c.Rfullp, n, Xo, n));
+      CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, n, rb, 1.0, c.Rfullp, n, Xo, n));
+    } else if (!c.blocks) {
+      thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, 0, 0, n, n, rb, 1.0, Bi, 0.0, w1);
+      thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, 0, 0, n, n, rb, 1.0, w1, 0.0, Xo);
+    } else {
+      const int64_t h2 = n - h1;
+      double* w2 = c.w2;
+      thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, 0, 0, h1, h1, rb, 1.0, Bi, 0.0, w1);                          // y1 = R11^-T b1
+      CAPITAL_CHECK(capi_dlacpy(h, 0, h2, rb, Bi + h1, n, w2 + h1, n));
+      thin(Rp, CAPI_RECT, CAPI_TRANS, 0, h1, h1, h2, rb, -1.0, w1, 1.0, w2 + h1);                      // b2 - R12^T y1
+      thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, h1, h1, h2, h2, rb, 1.0, w2 + h1, 0.0, w1 + h1);             // y2 = R22^-T (..)
+      thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, h1, h1, h2, h2, rb, 1.0, w1 + h1, 0.0, Xo + h1);           // x2 = R22^-1 y2
+      thin(Rp, CAPI_RECT, CAPI_NOTRANS, 0, h1, h1, h2, rb, -1.0, Xo + h1, 1.0, w1);                    // y1 - R12 x2
+      thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, 0, 0, h1, h1, rb, 1.0, w1, 0.0, Xo);                       // x1 = R11^-1 (..)
+    }
+  }
+  // the preconditions of everything that uses the factors; `who` opens the message
+  template <typename ArgType, typename CommType>
+  static void require_factors(ArgType& args, CommType&& CommInfo, const std::string& who) {
+    if (CommInfo.size > 1) throw std::logic_error(who + " is built for one rank: on a grid the factors are element-cyclic (factor there, solve on one rank)");
+    if (!&capi_dtrmm_thin || !&capi_dresid_ts) throw std::logic_error("cholinv: this C-ABI library has no capi_dtrmm_thin / capi_dresid_ts: no solve");
+    if (args.solve_by_substitution && !&capi_dtrsm_thin) throw std::logic_error("cholinv: this C-ABI library has no capi_dtrsm_thin: no solve by substitution");
+    if (!args.factored || args.potrf_info != 0 || !args.R.filled() || (!args.solve_with_trsm && !args.Rinv.filled()))
+      throw std::logic_error(who + ": factor() has not run or did not succeed: there are no valid factors to solve with");
+    if (args.factored_trsm != args.solve_with_trsm)
+      throw std::logic_error(who + ": solve_with_trsm was changed after factor(): the resident factors are those of the other mode; factor() again");
+  }
+  static void require_bounds_abi() {
+    if (!&capi_dsym_abs || !&capi_dberr || !&capi_dcolamax || !&capi_dlacn_block || !&capi_dlacn_state_bytes || !&capi_dresid_sym)
+      throw std::logic_error("cholinv: this C-ABI library has no capi_dsym_abs / capi_dberr / capi_dcolamax / capi_dlacn_block: no condition estimate, no error bounds");
+  }
+  // the estimator's loop over the shared operator: est (device, rb doubles) <- the estimates for the weight columns Wt (or none).  Returns the products
+  template <typename ArgType>
+  static int estimate(ArgType& args, const applier& ap, int64_t rb, const double* Wt, double* est) {
+    const int64_t n = ap.n;
+    double *v = args.BoundsV1.data(), *y = args.BoundsV2.data();
+    int active = 0, applies = 0;
+    CAPITAL_CHECK(capi_dlacn_block(ap.h, 1, n, rb, v, n, Wt, n, args.BoundsState.data(), est, &active));
+    while (active > 0) {
+      apply_inverse(ap, v, y, rb);
+      ++applies;
+      std::swap(v, y);
+      CAPITAL_CHECK(capi_dlacn_block(ap.h, 0, n, rb, v, n, Wt, n, args.BoundsState.data(), est, &active));
+    }
+    return applies;
+  }
+  template <typename ArgType>
+  static void register_bounds_work(ArgType& args, bool weights) {
+    const int64_t W = CAPI_TS_MAX_RHS, n = args.localDimension;
+    args.BoundsV1._register_(W, n, 1, 1);
+    args.BoundsV2._register_(W, n, 1, 1);
+    args.BoundsState._register_((int64_t)((capi_dlacn_state_bytes(n, W) + 7) / 8), 1, 1, 1);
+    args.BoundsSmall._register_(4 * W, 1, 1, 1);
+    if (weights) { args.BoundsRho._register_(W, n, 1, 1); args.BoundsWt._register_(W, n, 1, 1); }
+  }
+  template <typename ArgType>
+  static void release_bounds_work(ArgType& args) {
+    if (IP::keep_arena) return;
+    capital::sync();
+    args.SolveW1._destroy_(); args.SolveW2._destroy_();
+    args.BoundsRho._destroy_(); args.BoundsWt._destroy_(); args.BoundsV1._destroy_(); args.BoundsV2._destroy_(); args.BoundsState._destroy_();
+    args.BoundsSmall._destroy_();
+  }
+
   // event slots of the top-level overlap (matmult::summa's pipe uses slots below 1000)
   static constexpr int EV_INPUT_HEAD = 1020, EV_INPUT_REST = 1021, EV_TOP_R12 = 1022, EV_EARLY_PACK = 1023, EV_INPUT_MID = 1019;
   // lookahead (single GPU): slot + depth; the bulk streams are stream indices LA_STREAM0 + depth

@@ -187,6 +187,41 @@ int capi_dtrsm_thin(capi_handle_t h, int trans, int64_t n, int64_t r, const doub
  * about 128 p n bytes, 93 MiB at n = 32768 on 256 CUs (p = 22), 2 % of the triangle.  From 8 on: capi_dtrmm_thin's, and n x r doubles. */
 int capi_dresid_sym(capi_handle_t h, int64_t n, int64_t r, const double* A, int64_t lda, const double* X, int64_t ldx,
                     const double* B, int64_t ldb, double* Rout, int64_t ldr, double* colnorm2);
+/* ---- how far to trust a solve: the pieces of cholesky::cholinv::condition / error_bounds (LAPACK's dpocon and dporfs around products with the
+ * resident factors).  Not in the reference: cholinv.hpp stops at R and R^-1.  The conventions are those of the thin calls above: device pointers,
+ * column-major, 1 <= r <= CAPI_TS_MAX_RHS (else CAPI_EINVAL, nothing is touched), pointers aligned to 8 bytes, any leading dimension >= the
+ * rows, sums in a fixed order (bit-identical from run to run, no atomics), workspace of the handle's own. ---- */
+/* capi_dsym_abs: W (n x r) <- |S| |X| + |B| and colmax[j] <- max_i W(i, j) (DEVICE, r doubles) for the symmetric S given by the upper triangle of the
+ * column-major A, exactly as in capi_dresid_sym: dporfs's componentwise weights.  Not in the reference: cholinv.hpp stops at R and R^-1.
+ * B == NULL: the product alone; W == NULL: the maxima alone; colmax == NULL: W alone; n == 0: colmax <- 0.  X = ones and B = NULL give
+ * ||S||_1 in colmax[0].  NO element below A's diagonal influences any output: it may hold NaN (unwanted elements are removed by a select, never
+ * multiplied by zero).  A NaN in W shows in colmax.  W must not alias X; W == B is allowed.  The kernel is capi_dresid_sym's fused kernel on absolute
+ * values, at every r: 16 columns a pass, so the triangle is read from HBM ceil(r / 16) times.  Workspace: capi_dresid_sym's below 8 columns. */
+int capi_dsym_abs(capi_handle_t h, int64_t n, int64_t r, const double* A, int64_t lda, const double* X, int64_t ldx,
+                  const double* B, int64_t ldb, double* W, int64_t ldw, double* colmax);
+/* capi_dberr: dporfs's two elementwise steps in one pass over the residual Rho = B - S X (n x r) and the weights W = |S| |X| + |B| (capi_dsym_abs).
+ * Not in the reference: cholinv.hpp stops at R and R^-1.  berr[j] (DEVICE, r doubles) <- max_i |rho_ij| / w_ij where w_ij > safe2, and
+ * (|rho_ij| + safe1) / (w_ij + safe1) elsewhere, safe1 = (n + 1) DBL_MIN, safe2 = safe1 / eps, eps = 2^-53: the componentwise backward error.
+ * Then W(i, j) <- |rho_ij| + (n + 1) eps w_ij (+ safe1 where w_ij <= safe2): the weights of the forward bound (capi_dlacn_block's Wt).
+ * One workgroup per column; n == 0: berr <- 0.  W must not alias Rho.  No workspace. */
+int capi_dberr(capi_handle_t h, int64_t n, int64_t r, const double* Rho, int64_t ldr, double* W, int64_t ldw, double* berr);
+/* capi_dcolamax: colmax[j] (DEVICE, r doubles) <- max_i |X(i, j)|, a NaN showing: the ||x_j||_inf that scales a forward bound.  Not in the reference:
+ * cholinv.hpp stops at R and R^-1.  n == 0: zeros.  No workspace. */
+int capi_dcolamax(capi_handle_t h, int64_t n, int64_t r, const double* X, int64_t ldx, double* colmax);
+/* capi_dlacn_block: the Hager-Higham estimator of a 1-norm (LAPACK dlacn2, Higham's refinements included) for r operators at once, by reverse
+ * communication.  Not in the reference: cholinv.hpp stops at R and R^-1.  Column j estimates the 1-norm of diag(Wt(:, j)) Z -- which is
+ * || Z diag(Wt(:, j)) ||_inf, dporfs's bound on || |Z| w ||_inf -- for a SYMMETRIC operator Z that the caller applies (cholinv: Z = A^-1);
+ * Wt == NULL: ||Z||_1 itself.  Protocol: call with init = 1; while *active_host > 0, overwrite all r columns of X (n x r, ldx) with Z X and call
+ * again with init = 0; when *active_host == 0, est[j] (DEVICE, r doubles) holds the estimates.  One launch moves every column by its own dlacn2
+ * transition, so r estimates cost the products of the slowest column: at most 11.  The scaling by Wt happens inside (before the product for the
+ * transposed operator, after it otherwise): the caller applies Z alone.  A finished column is frozen: its column of X is zero, its est is not
+ * written again.  The call synchronises the handle's stream to return *active_host; that int is the only host traffic.  A state that is not
+ * this estimator's (more than 11 products behind it, say) gives CAPI_EINVAL.  n >= 1.  `state` is DEVICE memory of capi_dlacn_state_bytes(n, r)
+ * bytes (0 for arguments out of range), opaque, and belongs to one estimate from init to the end: per column the signs of the last sign vector, the
+ * stage, the round, the two last positions of the maximum and the estimate.  One workgroup per column, sums in a fixed order, the FIRST maximum. */
+size_t capi_dlacn_state_bytes(int64_t n, int64_t r);
+int capi_dlacn_block(capi_handle_t h, int init, int64_t n, int64_t r, double* X, int64_t ldx, const double* Wt, int64_t ldw,
+                     double* state, double* est, int* active_host);
 /* LAPACKE_dgeqrf / LAPACKE_dorgqr behind lapack::engine::_geqrf / _orgqr (lapack/interface.hpp:60-88; the reference has
  * the slots but no caller -- CholeskyQR2 is its QR).  Householder QR, LAPACK storage: R in the upper triangle, the
  * reflectors v_j (unit first entry implied) below it, tau[min(m,n)] on the DEVICE.  capi_dorgqr overwrites A (m x n,

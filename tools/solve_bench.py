@@ -22,11 +22,13 @@ on the factor itself (a synthetic, well-conditioned triangle), alternating:
   (c) capi_dtrmm_thin(CAPI_UPPERTRI) on a packed triangle (the inverse mode's product with R^-1) and the copy of the triangle's bytes
 
 and with --subst-e2e N Cholinv.solve with refine = 0 and 1, substitution off and on, in both factor modes (Serialize + SaveIntermediates: the only
-packed configuration in which the TRSM mode solves with the flag off).  With --e2e N one Cholinv.solve
+packed configuration in which the TRSM mode solves with the flag off).  With --bounds N the condition estimate and the error bounds: capi_dsym_abs
+beside capi_dresid_sym and the copy at r = 1, 8, 32, then Cholinv.rcond() and solve_expert beside solve in both factor modes (--orders "" runs it
+alone).  With --e2e N one Cholinv.solve
 (config 2's policies: complete_inv = 0, split = 1, Serialize) beside its factor().  The parent process makes no GPU call: every order runs in a
 child of its own under a time limit, and a failed child ends the run.
 
-    python tools/solve_bench.py [--reps 9] [--orders 16384,32768] [--resid 16384,32768] [--subst 32768] [--subst-e2e 32768] [--e2e 32768] [--limit 300]"""
+    python tools/solve_bench.py [--reps 9] [--orders 16384,32768] [--resid 16384,32768] [--subst 32768] [--subst-e2e 32768] [--e2e 32768] [--bounds 32768] [--limit 300]"""
 import argparse
 import os
 import statistics
@@ -286,6 +288,105 @@ def subst_e2e(n):
         driver.finalize()
 
 
+def bounds_child(n, reps, warmup):
+    """condition estimate and error bounds: the |.| pass beside the residual pass and the copy, then Cholinv.rcond() and solve_expert beside solve"""
+    import ctypes as C
+    import numpy as np
+    import torch
+    from capital_amd import capi, driver
+    h = capi.Handle(0)
+    dev = "cuda:0"
+    g = torch.Generator(device=dev).manual_seed(4)
+    p = capi.ptr
+    A = torch.empty((n, n), dtype=torch.float64, device=dev)
+    for j0 in range(0, n, 4096):
+        A[j0:j0 + 4096] = torch.randn((min(4096, n - j0), n), dtype=torch.float64, device=dev, generator=g) * (1.0 / n ** 0.5)
+    A = torch.triu(A)
+    A += torch.triu(A, 1).T
+    np_ = n * (n + 1) // 2
+    h.sync()
+    ms = C.c_float()
+
+    def timed(fn):
+        h.call("capi_timer_start")
+        fn()
+        h.call("capi_timer_stop_ms", C.byref(ms))
+        return ms.value
+
+    print(f"== |A| |X| + |B| pass, n = {n}: the upper triangle is {8 * np_ / 1e9:.2f} GB; {reps} alternating rounds after {warmup} warm-up rounds; "
+          f"capi version {h.L.capi_version()}", flush=True)
+    for r in (1, 8, 32):
+        X = torch.randn((r, n), dtype=torch.float64, device=dev, generator=g)
+        B = torch.randn((r, n), dtype=torch.float64, device=dev, generator=g)
+        Wa, Rb = capi.zeros(n, r), capi.zeros(n, r)
+        ma, nb = torch.zeros(r, dtype=torch.float64, device=dev), torch.zeros(r, dtype=torch.float64, device=dev)
+        csrc = torch.empty(np_ // 2, dtype=torch.float64, device=dev).normal_()
+        cdst = torch.empty_like(csrc)
+        steps = {
+            "a.dsym_abs": lambda: h.call("capi_dsym_abs", n, r, p(A), n, p(X), n, p(B), n, p(Wa), n, p(ma)),
+            "b.dresid_sym": lambda: h.call("capi_dresid_sym", n, r, p(A), n, p(X), n, p(B), n, p(Rb), n, p(nb)),
+            "copy": lambda: cdst.copy_(csrc),
+        }
+        times = {k: [] for k in steps}
+        for i in range(warmup + reps):
+            for k, fn in steps.items():
+                tm = timed(fn)
+                if i >= warmup:
+                    times[k].append(tm)
+        h.sync()
+        ref = (A.abs() @ X.abs().T).T + B.abs() if n <= 32768 else None
+        if ref is not None:
+            print(f"-- r = {r}:  max |W - torch| / max W = {(Wa - ref).abs().max().item() / ref.max().item():.2e}, "
+                  f"max |colmax - max W| = {(ma - Wa.max(dim=1).values).abs().max().item():.1e}")
+        med = {k: statistics.median(v) for k, v in times.items()}
+        for k in steps:
+            ts = times[k]
+            print(f"   {k:16s} {statistics.median(ts):8.3f} ms [{min(ts):.3f} .. {max(ts):.3f}]   this / (b) = {med[k] / med['b.dresid_sym']:.2f}"
+                  f"   this / copy = {med[k] / med['copy']:.2f}")
+        print(f"   the copy moves {8 * np_ / 1e9:.2f} GB: {8 * np_ / med['copy'] / 1e9:.2f} TB/s at its median", flush=True)
+        del X, B, Wa, Rb, csrc, cdst, ref
+    del A
+    h.close()
+    torch.cuda.empty_cache()
+
+    driver.init(0, 0, 1, None, use_torch_stream=False)
+    try:
+        rng = np.random.default_rng(0)
+        print(f"== Cholinv.rcond() and solve_expert beside solve, n = {n}, Serialize + SaveIntermediates, complete_inv = 0, refine = 1: medians of {reps} "
+              f"alternating rounds after {warmup}, wall clock incl. the host copies of B and X")
+        for trsm in (False, True):
+            pr = driver.Cholinv(n, c=1, complete_inv=0, split=1, bc_mult=0 if n <= 2048 else -(max(n // 2048, 2).bit_length() - 1), trsm_mode=trsm)
+            pr.generate()
+            pr.factor()
+            mode = "TRSM" if trsm else "inverse"
+            v, out = [], None
+            for i in range(warmup + reps):
+                t0 = time.perf_counter()
+                out = pr.rcond(details=True)
+                if i >= warmup:
+                    v.append((time.perf_counter() - t0) * 1e3)
+            print(f"   {mode} mode rcond(): {statistics.median(v):8.2f} ms [{min(v):.2f} .. {max(v):.2f}]   rcond = {out[0]:.3e}, ||A||_1 = {out[1]:.3e}, "
+                  f"{out[2]} products with A^-1", flush=True)
+            for r in (1, 8, 32):
+                B = np.asfortranarray(rng.standard_normal((n, r)))
+                ts, te, res = [], [], None
+                for i in range(warmup + reps):
+                    t0 = time.perf_counter()
+                    pr.solve(B, refine=1, residual=True)
+                    t1 = time.perf_counter()
+                    res = pr.solve_expert(B, refine=1, residual=True)
+                    t2 = time.perf_counter()
+                    if i >= warmup:
+                        ts.append((t1 - t0) * 1e3)
+                        te.append((t2 - t1) * 1e3)
+                print(f"   {mode} mode r = {r:2d}: solve {statistics.median(ts):8.2f} ms [{min(ts):.2f} .. {max(ts):.2f}], solve_expert {statistics.median(te):8.2f} ms "
+                      f"[{min(te):.2f} .. {max(te):.2f}]: the bounds add {statistics.median(te) - statistics.median(ts):.2f} ms   "
+                      f"(max berr {res[3].max():.2e}, max ferr {res[2].max():.2e})", flush=True)
+            pr.close()
+    finally:
+        driver.finalize()
+
+
 def e2e(n):
     import numpy as np
     from capital_amd import driver
@@ -327,6 +428,7 @@ def main():
     ap.add_argument("--subst", default="", help="orders of the solve by substitution: capi_dtrsm_thin against capi_dtrsm, capi_dtrmm_thin and the copy")
     ap.add_argument("--subst-e2e", type=int, default=0, help="order of Cholinv.solve with substitution off and on, in both factor modes (0: none)")
     ap.add_argument("--e2e", type=int, default=0, help="order of one end-to-end factor() + solve (0: none)")
+    ap.add_argument("--bounds", type=int, default=0, help="order of the condition estimate and error bounds: capi_dsym_abs, Cholinv.rcond(), solve_expert (0: none)")
     ap.add_argument("--limit", type=int, default=300, help="seconds per child")
     ap.add_argument("--child", default=None)
     a = ap.parse_args()
@@ -337,13 +439,15 @@ def main():
             subst_child(int(a.child[6:]), a.reps, a.warmup)
         elif a.child.startswith("e2e:"):
             e2e(int(a.child[4:]))
+        elif a.child.startswith("bounds:"):
+            bounds_child(int(a.child[7:]), a.reps, a.warmup)
         elif a.child.startswith("resid:"):
             resid_child(int(a.child[6:]), a.reps, a.warmup)
         else:
             child(int(a.child), a.reps, a.warmup)
         return 0
     jobs = [o for o in a.orders.split(",") if o] + [f"resid:{o}" for o in a.resid.split(",") if o] + [f"subst:{o}" for o in a.subst.split(",") if o]
-    jobs += ([f"subst_e2e:{a.subst_e2e}"] if a.subst_e2e else []) + ([f"e2e:{a.e2e}"] if a.e2e else [])
+    jobs += ([f"subst_e2e:{a.subst_e2e}"] if a.subst_e2e else []) + ([f"e2e:{a.e2e}"] if a.e2e else []) + ([f"bounds:{a.bounds}"] if a.bounds else [])
     for job in jobs:
         try:
             rc = subprocess.run([sys.executable, "-u", os.path.abspath(__file__), "--child", job, "--reps", str(a.reps), "--warmup", str(a.warmup)],
