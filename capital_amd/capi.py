@@ -46,6 +46,7 @@ _SIGS = {
     "capi_dberr": [_i64, _i64, _vp, _i64, _vp, _i64, _vp],
     "capi_dcolamax": [_i64, _i64, _vp, _i64, _vp],
     "capi_dlacn_block": [_int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, C.POINTER(_int)],
+    "capi_dgesvj": [_i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(_int)],
     "capi_get_info": [C.POINTER(_int)],
     "capi_reset_info": [],
     "capi_serialize": [_int, _int, _vp, _i64, _i64, _vp, _i64, _i64] + [_i64] * 8,

@@ -71,6 +71,7 @@ def bind(D):
     D.capital_cacqr_set_shift.argtypes = [_vp, _int, _dbl]
     D.capital_cacqr_sweep_stats.argtypes = [_vp, _int, _dp]
     D.capital_cacqr_lstsq.argtypes = [_vp, _i64, _dp, _dp, _dp]
+    D.capital_cacqr_svd.argtypes = [_vp, _int, _dp, _dp, _dp, C.POINTER(_int)]
     return D
 
 
@@ -318,6 +319,20 @@ class Cacqr:
         res = np.zeros(r) if residual else None
         _ck(self.D.capital_cacqr_lstsq(self.p, r, b.ctypes.data_as(_dp), X.ctypes.data_as(_dp), res.ctypes.data_as(_dp) if residual else None), "lstsq")
         return X, res
+
+    def svd(self, left=True):
+        """The singular value decomposition of A on the factors of the last factor() (qr::cacqr::svd, 1-D variant): R = U_R diag(s) V^T by one-sided
+        Jacobi on the device (capi_dgesvj), then U = Q U_R on this rank's rows.  Returns (U_local or None, s, V) with A = U diag(s) V^T: U_local
+        m_loc x n (None with left=False, which touches no m x n memory), s the n singular values, descending, V n x n -- s and V the same bits on
+        every rank.  self.svd_sweeps: the Jacobi sweeps the call took."""
+        U = np.zeros((self.m_loc, self.n), order="F") if left else None
+        s = np.zeros(self.n)
+        V = np.zeros((self.n, self.n), order="F")
+        sw = _int()
+        _ck(self.D.capital_cacqr_svd(self.p, int(bool(left)), U.ctypes.data_as(_dp) if left else None, s.ctypes.data_as(_dp), V.ctypes.data_as(_dp),
+                                     C.byref(sw)), "svd")
+        self.svd_sweeps = sw.value
+        return U, s, V
 
     def residual(self):
         v = _dbl()

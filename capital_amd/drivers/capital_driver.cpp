@@ -136,6 +136,7 @@ struct cacqr_problem {
   virtual void set_shift(int num_shifted, double shift_scale) = 0;
   virtual void sweep_stats(int k, double* out3) = 0;
   virtual void lstsq(int64_t r, const double* B_host, double* X_host, double* resnorm_host) = 0;
+  virtual void svd(bool want_left, double* U_host, double* s_host, double* V_host, int* sweeps) = 0;
 };
 
 template <class Alg>
@@ -171,6 +172,16 @@ struct cacqr_impl : cacqr_problem {
     auto x = pack.X.to_host();
     std::memcpy(X_host, x.data(), sizeof(double) * x.size());
     if (resnorm_host) std::memcpy(resnorm_host, pack.ls_residual_norms.data(), sizeof(double) * (size_t)r);
+  }
+  // A = U diag(s) V^T on the factors of the last factor(): s_host receives the n singular values (descending), V_host (may be NULL) the n x n V,
+  // U_host, with want_left, this rank's m_loc x n block of U (column-major, rows dealt as A's); want_left == false touches no m x n memory
+  void svd(bool want_left, double* U_host, double* s_host, double* V_host, int* sweeps) override {
+    if (!s_host || (want_left && !U_host)) throw std::invalid_argument("cacqr svd: a place for the singular values, and for U with want_left, expected");
+    Alg::svd(pack, grid, want_left);
+    std::memcpy(s_host, pack.singular_values.data(), sizeof(double) * pack.singular_values.size());
+    if (V_host) { auto v = pack.V.to_host(); std::memcpy(V_host, v.data(), sizeof(double) * v.size()); }
+    if (want_left) { auto u = pack.U.to_host(); std::memcpy(U_host, u.data(), sizeof(double) * u.size()); }
+    if (sweeps) *sweeps = pack.svd_sweeps;
   }
   double residual() override { return qr::validate<Alg>::residual(A, pack, grid); }
   double orthogonality() override { return qr::validate<Alg>::orthogonality(A, pack, grid); }
@@ -306,6 +317,11 @@ int capital_cacqr_sweep_stats(void* p, int k, double* out3) { return guarded([&]
 // least squares on the factors (qr::cacqr::least_squares): after capital_cacqr_factor; resnorm_host_or_null == NULL skips the residual pass
 int capital_cacqr_lstsq(void* p, int64_t r, const double* B_host_local, double* X_host, double* resnorm_host_or_null) {
   return guarded([&] { ((cacqr_problem*)p)->lstsq(r, B_host_local, X_host, resnorm_host_or_null); });
+}
+// singular values and vectors on the factors (qr::cacqr::svd): after capital_cacqr_factor, c == 1.  A = U diag(s) V^T; s_host: n doubles; V_host_or_null:
+// n x n; U_host_local_or_null: this rank's m_loc x n rows of U, written with want_left != 0; sweeps (may be NULL): the Jacobi sweeps on R
+int capital_cacqr_svd(void* p, int want_left, double* U_host_local_or_null, double* s_host, double* V_host_or_null, int* sweeps) {
+  return guarded([&] { ((cacqr_problem*)p)->svd(want_left != 0, U_host_local_or_null, s_host, V_host_or_null, sweeps); });
 }
 int capital_cacqr_factor(void* p) { return guarded([&] { ((cacqr_problem*)p)->factor(); }); }
 int capital_cacqr_residual(void* p, double* out) { return guarded([&] { *out = ((cacqr_problem*)p)->residual(); }); }

@@ -26,6 +26,11 @@
 //     X = R^-1 C             capi_dtrsm on a full-storage image of R, replicated: identical bits in, identical bits out on every rank
 //     ||b_j - A x_j||^2      capi_dresid_ts on A (not Q), r doubles all-reduced, square roots on the host
 // No m x n temporary: the new device memory is B, X and the n x n image of R (the Gram work block, re-registered when the policy released it).
+// And svd(args, topo, left) after factor(): the singular values and vectors of A from the resident pair, A = Q R = (Q U_R) Sigma V^T (1-D variant only):
+//     R = U_R Sigma V^T      capi_dgesvj on a full-storage image of R: one-sided Jacobi on the device, deterministic, so that every rank computes the
+//                            same bits from its replicated R and nothing is communicated
+//     U = Q U_R              capi_dgemm on the local rows (left == true only)
+// New device memory: Sigma (n), V and U_R (n x n each) and, with left, U: ONE new m_loc x n block.  With left == false no m x n memory is touched.
 // Underneath, the A -> Q copy of factor() (cacqr.hpp:226) is folded into the first sweep (it reads A, writes Q) and the
 // second sweep ping-pongs between Q's data and scratch buffers, so every sweep streams the panel exactly twice
 // (read for the Gram, read+write for the solve) with no in-place hazard.
@@ -44,6 +49,8 @@
 // likewise the two streaming kernels of least_squares: without them factor() runs as before and least_squares refuses
 #pragma weak capi_dgemtn_ts
 #pragma weak capi_dresid_ts
+// and the device SVD of R under svd
+#pragma weak capi_dgesvj
 
 namespace qr {
 
@@ -89,6 +96,12 @@ public:
     matrix<ScalarType, DimensionType, rect> X, LsNorm2;
     std::vector<double> ls_residual_norms;
     bool factored = false;
+    // svd: A = U diag(singular_values) V^T.  Sigma (n, device) and V (n x n) are replicated on every rank, bit for bit; U (m_loc x n, this rank's
+    // rows, with left == true) = Q UR; svd_sweeps = the Jacobi sweeps capi_dgesvj ran; cond2 = sigma_1 / sigma_n
+    matrix<ScalarType, DimensionType, rect> U, Sigma, V, UR;
+    std::vector<double> singular_values;
+    int svd_sweeps = 0;
+    double cond2 = 0.0;
   };
 
   template <typename MatrixType, typename ArgType, typename CommType>
@@ -160,6 +173,37 @@ public:
     }
     if (!IP::keep_work) { capital::sync(); args.G._destroy_(); }
     CRITTER_STOP(CQR::lstsq);
+  }
+
+  // The singular value decomposition of the factored A on the pair factor() left: args.singular_values / args.Sigma, args.V and, with `left`,
+  // args.U (m_loc x n).  Nothing of the factorization is overwritten.  See the file comment.
+  template <typename ArgType, typename CommType>
+  static void svd(ArgType& args, CommType&& CommInfo, bool left = true) {
+    if (CommInfo.c != 1) throw std::logic_error("qr::cacqr::svd is built for the 1-D variant (c == 1) only");
+    if (!&capi_dgesvj) throw std::logic_error("qr::cacqr: this C-ABI library has no capi_dgesvj: no singular value decomposition");
+    if (!args.factored || args.potrf_info != 0 || !args.Q.filled() || !args.R.filled())
+      throw std::logic_error("qr::cacqr::svd: factor() has not run or did not succeed: there is no valid Q and R to decompose");
+    capi_handle_t h = capital::handle();
+    const int64_t n = args.Q.num_columns_global(), m_loc = args.Q.num_rows_local();
+    CRITTER_START(CQR::svd);
+    args.G._register_(n, n, 1, 1);                                                                                  // full-storage image of R
+    serialize<uppertri, uppertri>::invoke(args.R, args.G, 0, n, 0, n, 0, n, 0, n);
+    args.Sigma._register_(1, n, 1, 1);
+    args.V._register_(n, n, 1, 1);
+    if (left) args.UR._register_(n, n, 1, 1);
+    int sweeps = 0;
+    CAPITAL_CHECK(capi_dgesvj(h, n, args.G.data(), n, left ? args.UR.data() : nullptr, n, args.Sigma.data(), args.V.data(), n, &sweeps));
+    args.svd_sweeps = sweeps;
+    if (left) {
+      args.U._register_(n, args.Q.num_rows_global(), CommInfo.c, CommInfo.d);
+      CAPITAL_CHECK(capi_dgemm(h, CAPI_NOTRANS, CAPI_NOTRANS, m_loc, n, n, 1.0, args.Q.data(), m_loc, args.UR.data(), n, 0.0, args.U.data(), m_loc));   // U = Q U_R
+    }
+    args.singular_values = args.Sigma.to_host();
+    args.cond2 = args.singular_values.front() / args.singular_values.back();
+    if (!IP::keep_work) { capital::sync(); args.G._destroy_(); args.UR._destroy_(); }
+    CRITTER_STOP(CQR::svd);
+    if (sweeps < 0)
+      throw std::runtime_error("qr::cacqr::svd: the Jacobi sweeps on R did not converge within " + std::to_string(-sweeps) + " sweeps");
   }
 
   template <typename ArgType, typename CommType>

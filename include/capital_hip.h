@@ -222,6 +222,26 @@ int capi_dcolamax(capi_handle_t h, int64_t n, int64_t r, const double* X, int64_
 size_t capi_dlacn_state_bytes(int64_t n, int64_t r);
 int capi_dlacn_block(capi_handle_t h, int init, int64_t n, int64_t r, double* X, int64_t ldx, const double* Wt, int64_t ldw,
                      double* state, double* est, int* active_host);
+/* ---- the singular value decomposition of an upper triangular R (n x n, column-major, ldr >= n), R = U diag(sigma) V^T: the job of LAPACK's dgesvj
+ * for a triangle, and the last step of a tall-skinny SVD on the CholeskyQR factors (qr::cacqr::svd: A = Q R = (Q U) Sigma V^T).
+ * Not in the reference: cacqr.hpp stops at Q and R.  1 <= n <= 2048 (else CAPI_EINVAL, nothing is touched; n == 1 has no pairs).  Only R's upper triangle, diagonal
+ * included, is read: what lies below may be NaN and influences nothing; R is not written.  sigma (DEVICE, n doubles): non-negative, descending.
+ * U and V (n x n, ldu, ldv >= n) are written in full; either or both may be NULL (both: the values alone), and they must not alias each other.
+ * Method: one-sided (Hestenes) Jacobi on the columns of R^T, cyclic sweeps in round-robin order (csrc/jacobi_plan.h: N - 1 steps of up to N / 2
+ * disjoint pairs, N = n rounded up to even) -- one launch per step, one workgroup per pair.  A pair is rotated when |x^T y| > sqrt(n) 2^-53 ||x|| ||y||
+ * (dgesvj's criterion) and skipped when a column is zero; the first sweep that rotates nothing ends the loop, the 30th at the latest.
+ * *sweeps_host receives the number of sweeps run, or -30 when the cap was hit: the call then still sorts and returns what it has, with CAPI_OK.
+ * The normalised final columns are V and their norms sigma, so V costs nothing beyond the values; U is the product of the rotations, accumulated
+ * only when U != NULL (two more columns per rotation), and polished by one Newton-Schulz step U (1.5 I - 0.5 U^T U) -- two n x n products on the tile
+ * kernel.  Then a stable descending sort, ties by index (a NaN sorts first); a column whose norm is exactly zero stays zero.  No sign convention.
+ * Steps are ordered by kernel boundaries on the handle's stream: no cooperative launch, no device-side waiting; sums have a fixed order and the only
+ * atomics are the integer counts of a sweep's rotations, so every result is bit-identical from run to run and on every device that holds the same R.
+ * The call synchronises the stream once per sweep to read that count (4 bytes), the only host traffic.  Non-finite input: a NaN compares false,
+ * rotates nothing and comes back as NaN in sigma.  Accuracy as measured: an O(sweeps n u) normwise error, residual and sigma errors
+ * of 3e-14 to 1e-13 at n = 256 where LAPACK's bidiagonal SVD gives 2e-15.  Pointers aligned to 8 bytes.
+ * Workspace, of the handle's own: n x n doubles (2 n x n with U) and 2 n more. */
+int capi_dgesvj(capi_handle_t h, int64_t n, const double* R, int64_t ldr, double* U, int64_t ldu, double* sigma, double* V, int64_t ldv,
+                int* sweeps_host);
 /* LAPACKE_dgeqrf / LAPACKE_dorgqr behind lapack::engine::_geqrf / _orgqr (lapack/interface.hpp:60-88; the reference has
  * the slots but no caller -- CholeskyQR2 is its QR).  Householder QR, LAPACK storage: R in the upper triangle, the
  * reflectors v_j (unit first entry implied) below it, tau[min(m,n)] on the DEVICE.  capi_dorgqr overwrites A (m x n,

@@ -1,0 +1,45 @@
+"""One rank of a tall-skinny SVD on several ranks (tests/test_gpu_cacqr_svd.py), in the style of tests/_gpu_lstsq_rank_main.py: a fresh process,
+torch.distributed (gloo) only to ship the communicator's unique id, everything else through the product's driver.  Every rank builds the same
+seeded panel (tests/_scqr_ref.py), keeps its rows r, r + P, .. of A, factors, decomposes, and saves its rows of U with s and V."""
+import datetime
+import json
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+
+import _scqr_ref as ref  # noqa: E402
+
+
+def main():
+    cfg = json.loads(sys.argv[1])
+    rank, world, local = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"]), int(os.environ["LOCAL_RANK"])
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    import torch
+    import torch.distributed as dist
+    torch.cuda.set_device(local)
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=int(os.environ.get("CAPITAL_TEST_GLOO_TIMEOUT_S", "300"))))
+    from capital_amd import driver
+    driver.init_distributed(local)
+    for case in cfg["cases"]:
+        print(f"rank {rank}: case {case['tag']} starts", flush=True)
+        A = ref.panel(case["m"], case["n"], case["kappa"], 0)
+        q = driver.Cacqr(case["m"], case["n"], c=1, variant=case["sweeps"], shifted=case["shifted"])
+        q.set_A(np.asfortranarray(A[rank::world]))
+        q.factor()
+        U, s, V = q.svd()
+        np.savez(os.path.join(cfg["dir"], f"{case['tag']}_rank{rank}.npz"), U=U, s=s, V=V, sweeps=q.svd_sweeps)
+        q.close()
+        dist.barrier()
+    driver.finalize()
+    dist.barrier()
+    dist.destroy_process_group()
+    print(f"rank {rank} ok", flush=True)
+
+
+if __name__ == "__main__":
+    main()
