@@ -47,6 +47,8 @@ _SIGS = {
     "capi_dcolamax": [_i64, _i64, _vp, _i64, _vp],
     "capi_dlacn_block": [_int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, C.POINTER(_int)],
     "capi_dgesvj": [_i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(_int)],
+    "capi_dpstrf": [_i64, _vp, _i64, _dbl, _vp, C.POINTER(_int)],
+    "capi_drow_scatter": [_int, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64],
     "capi_get_info": [C.POINTER(_int)],
     "capi_reset_info": [],
     "capi_serialize": [_int, _int, _vp, _i64, _i64, _vp, _i64, _i64] + [_i64] * 8,

@@ -72,6 +72,8 @@ def bind(D):
     D.capital_cacqr_sweep_stats.argtypes = [_vp, _int, _dp]
     D.capital_cacqr_lstsq.argtypes = [_vp, _i64, _dp, _dp, _dp]
     D.capital_cacqr_svd.argtypes = [_vp, _int, _dp, _dp, _dp, C.POINTER(_int)]
+    D.capital_cacqr_factor_pivoted.argtypes = [_vp, _dbl, _dbl, C.POINTER(_int)]
+    D.capital_cacqr_get_piv.argtypes = [_vp, C.POINTER(_i64)]
     return D
 
 
@@ -277,6 +279,7 @@ class Cacqr:
         if not self.p:
             raise DriverError("capital_cacqr_create: " + self.D.capital_drv_last_error().decode())
         self.variant, self.shifted = variant, shifted
+        self.rank, self.piv = 0, None
         if shifted or shift_scale != 1.0:
             _ck(self.D.capital_cacqr_set_shift(self.p, shifted, shift_scale), "set_shift")
         ml, nn = _i64(), _i64()
@@ -293,6 +296,28 @@ class Cacqr:
 
     def factor(self):
         _ck(self.D.capital_cacqr_factor(self.p), "factor")
+
+    def factor_pivoted(self, rtol=0.0, tol_scale=1.0):
+        """Column-pivoted CholeskyQR for a panel whose columns may be linearly dependent (qr::cacqr::factor_pivoted, 1-D variant): A[:, piv] = Q R with Q
+        m x rank orthonormal and R rank x n upper trapezoidal.  A column is dropped when, after projecting out the accepted ones, its squared norm is at
+        most tol trace(A^T A), tol = tol_scale max(rtol^2, 11 (m n + n (n + 1)) u): relative to ||A||_F the rank threshold is sqrt(tol), the Gram matrix's
+        own noise level (about 1e-5 at 2048 x 32) -- rtol above it gives a truncated pivoted QR.  Returns the numerical rank; afterwards .rank, .piv,
+        R_pivoted(), Q_pivoted(), and lstsq() gives the basic solution (zeros in the dropped columns)."""
+        rk = _int(0)
+        self.rank, self.piv = 0, None
+        _ck(self.D.capital_cacqr_factor_pivoted(self.p, float(rtol), float(tol_scale), C.byref(rk)), "factor_pivoted")
+        piv = np.zeros(self.n, dtype=np.int64)
+        _ck(self.D.capital_cacqr_get_piv(self.p, piv.ctypes.data_as(C.POINTER(_i64))), "get_piv")
+        self.rank, self.piv = rk.value, piv
+        return self.rank
+
+    def R_pivoted(self):
+        """R of the last factor_pivoted(), rank x n upper trapezoidal: A[:, piv] = Q_pivoted() @ R_pivoted(); the same bits on every rank"""
+        return np.asfortranarray(self._get(4, (self.n, self.n))[:self.rank])
+
+    def Q_pivoted(self):
+        """this rank's rows of the orthonormal factor of the last factor_pivoted(), m_loc x rank"""
+        return np.asfortranarray(self._get(1, (self.m_loc, self.n))[:, :self.rank])
 
     def sweep_stats(self):
         """Per sweep of the last factor() of a run with shifted sweeps: the shift s, the trace of the equilibrated Gram matrix (both 0

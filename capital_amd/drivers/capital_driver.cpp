@@ -137,6 +137,8 @@ struct cacqr_problem {
   virtual void sweep_stats(int k, double* out3) = 0;
   virtual void lstsq(int64_t r, const double* B_host, double* X_host, double* resnorm_host) = 0;
   virtual void svd(bool want_left, double* U_host, double* s_host, double* V_host, int* sweeps) = 0;
+  virtual void factor_pivoted(double rtol, double tol_scale, int* rank) = 0;
+  virtual void get_piv(int64_t* piv_host) = 0;
 };
 
 template <class Alg>
@@ -183,15 +185,44 @@ struct cacqr_impl : cacqr_problem {
     if (want_left) { auto u = pack.U.to_host(); std::memcpy(U_host, u.data(), sizeof(double) * u.size()); }
     if (sweeps) *sweeps = pack.svd_sweeps;
   }
-  double residual() override { return qr::validate<Alg>::residual(A, pack, grid); }
-  double orthogonality() override { return qr::validate<Alg>::orthogonality(A, pack, grid); }
+  // column-pivoted CholeskyQR (qr::cacqr::factor_pivoted): rtol = the user's tolerance relative to ||A||_F (0: the floor alone), tol_scale multiplies
+  // the tolerance; *rank (may be NULL) receives the numerical rank, also when the call throws behind capi_dpstrf
+  void factor_pivoted(double rtol, double tol_scale, int* rank) override {
+    pack.pivot_rtol = rtol;
+    pack.pivot_tol_scale = tol_scale;
+    if (rank) *rank = 0;
+    try {
+      Alg::factor_pivoted(A, pack, grid);
+    } catch (...) {
+      if (rank) *rank = (int)pack.rank;
+      throw;
+    }
+    if (rank) *rank = (int)pack.rank;
+  }
+  void get_piv(int64_t* piv_host) override {
+    if (!piv_host || pack.piv.empty()) throw std::invalid_argument("cacqr get_piv: factor_pivoted has not run (or no place for the n indices)");
+    for (size_t j = 0; j < pack.piv.size(); ++j) piv_host[j] = pack.piv[j];
+  }
+  // the validators and which = 2 / 3 of get() read factor()'s pair (a square R, n columns of Q): not what factor_pivoted leaves
+  void plain_factors_only(const char* what) const {
+    if (pack.pivoted) throw std::logic_error(std::string("cacqr ") + what + ": the resident factors are factor_pivoted's; use get which = 4 (Rp), 1 (Q) and get_piv");
+  }
+  double residual() override { plain_factors_only("residual"); return qr::validate<Alg>::residual(A, pack, grid); }
+  double orthogonality() override { plain_factors_only("orthogonality"); return qr::validate<Alg>::orthogonality(A, pack, grid); }
   void get(int which, double* host) override {
     if (which == 0) { auto v = A.to_host(); std::memcpy(host, v.data(), sizeof(double) * v.size()); return; }
+    if (which == 2 || which == 3) plain_factors_only("get");
     if (which == 1) { auto v = Alg::construct_Q(pack, grid).to_host(); std::memcpy(host, v.data(), sizeof(double) * v.size()); return; }
     if (which == 3) {                                     // Q^T Q (summed over the ranks), n x n
       matrix<double, int64_t, rect> I(A.num_columns_global(), A.num_columns_global(), 1, 1);
       qr::validate<Alg>::gram_of_Q(pack, grid, I);
       auto v = I.to_host();
+      std::memcpy(host, v.data(), sizeof(double) * v.size());
+      return;
+    }
+    if (which == 4) {                                     // Rp of factor_pivoted, n x n: rows < rank hold R, the rest is zero
+      if (!pack.pivoted || !pack.Rp.filled()) throw std::invalid_argument("cacqr get: which = 4 (Rp) needs a successful factor_pivoted");
+      auto v = pack.Rp.to_host();
       std::memcpy(host, v.data(), sizeof(double) * v.size());
       return;
     }
@@ -323,6 +354,13 @@ int capital_cacqr_lstsq(void* p, int64_t r, const double* B_host_local, double* 
 int capital_cacqr_svd(void* p, int want_left, double* U_host_local_or_null, double* s_host, double* V_host_or_null, int* sweeps) {
   return guarded([&] { ((cacqr_problem*)p)->svd(want_left != 0, U_host_local_or_null, s_host, V_host_or_null, sweeps); });
 }
+// column-pivoted CholeskyQR for panels that may be rank deficient (qr::cacqr::factor_pivoted, c == 1): *rank (may be NULL) receives the numerical rank;
+// afterwards capital_cacqr_get_piv gives the n column indices (column j of A P is column piv[j] of A), capital_cacqr_get which = 4 the n x n Rp
+// and which = 1 Q (its first rank columns), and capital_cacqr_lstsq the basic least-squares solution
+int capital_cacqr_factor_pivoted(void* p, double rtol, double tol_scale, int* rank) {
+  return guarded([&] { ((cacqr_problem*)p)->factor_pivoted(rtol, tol_scale, rank); });
+}
+int capital_cacqr_get_piv(void* p, int64_t* piv_host) { return guarded([&] { ((cacqr_problem*)p)->get_piv(piv_host); }); }
 int capital_cacqr_factor(void* p) { return guarded([&] { ((cacqr_problem*)p)->factor(); }); }
 int capital_cacqr_residual(void* p, double* out) { return guarded([&] { *out = ((cacqr_problem*)p)->residual(); }); }
 int capital_cacqr_orthogonality(void* p, double* out) { return guarded([&] { *out = ((cacqr_problem*)p)->orthogonality(); }); }

@@ -31,6 +31,22 @@
 //                            same bits from its replicated R and nothing is communicated
 //     U = Q U_R              capi_dgemm on the local rows (left == true only)
 // New device memory: Sigma (n), V and U_R (n x n each) and, with left, U: ONE new m_loc x n block.  With left == false no m x n memory is touched.
+// And factor_pivoted(A, args, topo) beside factor(): a column-pivoted CholeskyQR for panels whose columns are linearly dependent, A P = Q R with Q
+// m x k orthonormal, R k x n upper trapezoidal and k the numerical rank -- dgeqp3 / dgelsy semantics on the CholeskyQR scheme (1-D variant only):
+//     G = A^T A, all-reduced     exactly as in a plain sweep
+//     P^T G P = R^T R + (0, S)   capi_dpstrf in capi_dpotrf_trtri's place: Cholesky with diagonal pivoting, stopped at rank k where the largest
+//                                remaining Schur diagonal is <= tol trace(G), tol = pivot_tol_scale max(pivot_rtol^2, 11 (m n + n (n + 1)) u) -- the
+//                                floor is the factor of the shift a shifted sweep would add: a column is dropped when, after projecting out the
+//                                accepted ones, its squared norm is at most that shift.  Replicated: every rank computes the same bits
+//     M = P(:, 0:k) R11^-1       capi_dtrtri on a copy of the leading block, capi_drow_scatter (n x k)
+//     Q1 = A M                   capi_dgemm, m_loc x n x k: dense where a plain sweep's product is triangular
+//     Q = Q1 R2^-1               one plain sweep on the m_loc x k panel
+//     Rp(0:k, :) = R2 [R11 R12]  capi_dtrmm_oop (left, upper); rows >= k of Rp are zero
+// so that A(:, piv[j]) = Q Rp(:, j) up to ||A P - Q R||_F <= sqrt((n - k) tol trace(G)) plus rounding.  The resolution is the Gram matrix's own noise
+// level: relative to ||A||_F the rank threshold is sqrt(tol), about 1e-5 at 2048 x 32 and about 1e-3 at 2^22 x 256 -- a singular value below that
+// cannot be told from zero here, where dgeqp3 on A itself resolves down to u.  pivot_rtol above the floor gives a truncated pivoted QR, a low-rank
+// approximation with that error bound.  least_squares() after it returns the BASIC solution: X = P [R11^-1 (Q^T B); 0], zeros in the dropped
+// columns (not the minimum-norm one); svd() after it refuses.
 // Underneath, the A -> Q copy of factor() (cacqr.hpp:226) is folded into the first sweep (it reads A, writes Q) and the
 // second sweep ping-pongs between Q's data and scratch buffers, so every sweep streams the panel exactly twice
 // (read for the Gram, read+write for the solve) with no in-place hazard.
@@ -51,6 +67,9 @@
 #pragma weak capi_dresid_ts
 // and the device SVD of R under svd
 #pragma weak capi_dgesvj
+// and the pivoted Cholesky and the permutation kernel under factor_pivoted
+#pragma weak capi_dpstrf
+#pragma weak capi_drow_scatter
 
 namespace qr {
 
@@ -69,7 +88,8 @@ public:
     using cholesky_inverse_type = CholeskyInversionType;
     template <typename CholeskyInversionArgType>
     info(size_t num_iter, CholeskyInversionArgType&& ci_args) : num_iter(num_iter), cholesky_inverse_args(std::forward<CholeskyInversionArgType>(ci_args)) {}
-    info(const info& p) : num_iter(p.num_iter), num_shifted(p.num_shifted), shift_scale(p.shift_scale), cholesky_inverse_args(p.cholesky_inverse_args) {}
+    info(const info& p) : num_iter(p.num_iter), num_shifted(p.num_shifted), shift_scale(p.shift_scale), cholesky_inverse_args(p.cholesky_inverse_args),
+                          pivot_rtol(p.pivot_rtol), pivot_tol_scale(p.pivot_tol_scale) {}
     const size_t num_iter;                                                       // 1: CholeskyQR, 2: CholeskyQR2 (bench/qr/cacqr.cpp:14,40); up to 4 sweeps
     size_t num_shifted = 0;                                                      // the first num_shifted sweeps are shifted (1-D variant); see the file comment
     double shift_scale = 1.0;                                                    // multiplies the published shift 11 (m n + n (n + 1)) u ||A D^-1||_F^2
@@ -102,6 +122,15 @@ public:
     std::vector<double> singular_values;
     int svd_sweeps = 0;
     double cond2 = 0.0;
+    // factor_pivoted: tol = pivot_tol_scale * max(pivot_rtol^2, 11 (m n + n (n + 1)) u) (pivot_rtol: the user's tolerance relative to ||A||_F, 0 = the
+    // floor alone).  rank = the numerical rank k; piv (host) / Piv (device: n ints in the first (n + 1) / 2 doubles): column j of A P is column piv[j] of A;
+    // Rp (n x n): rows < rank hold R, the rest is zero; Q's first rank columns are the orthonormal factor; pivot_tol: the tol that
+    // went into capi_dpstrf (thresh = pivot_tol trace(A^T A)); pivoted: the resident factors are factor_pivoted's (factor() clears it)
+    double pivot_rtol = 0.0, pivot_tol_scale = 1.0, pivot_tol = 0.0;
+    int64_t rank = 0;
+    std::vector<int> piv;
+    matrix<ScalarType, DimensionType, rect> Piv, Rp;
+    bool pivoted = false;
   };
 
   template <typename MatrixType, typename ArgType, typename CommType>
@@ -127,6 +156,98 @@ public:
     args.factored = true;
   }
 
+  // Column-pivoted CholeskyQR of a panel that may be rank deficient: args.rank = k, args.piv / args.Piv, the m_loc x k orthonormal factor in the
+  // first k columns of args.Q and the k x n trapezoid in args.Rp, A(:, piv[j]) = Q Rp(:, j).  See the file comment.  std::domain_error when the
+  // numerical rank is 0 (A is zero or not finite) or the plain sweep on the rank-k panel breaks down.
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void factor_pivoted(const MatrixType& A, ArgType& args, CommType&& CommInfo) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "qr::cacqr requires matrices of rect structure");
+    using Dim = typename MatrixType::DimensionType;
+    if (CommInfo.c != 1) throw std::logic_error("qr::cacqr::factor_pivoted is built for the 1-D variant (c == 1) only");
+    if (!&capi_dpstrf || !&capi_drow_scatter)
+      throw std::logic_error("qr::cacqr: this C-ABI library has no capi_dpstrf / capi_drow_scatter: no pivoted factorization");
+    const int64_t n = A.num_columns_global(), m_loc = A.num_rows_local(), m_glob = A.num_rows_global();
+    if (n < 1 || n > 2048) throw std::invalid_argument("qr::cacqr::factor_pivoted: 1 <= n <= 2048 columns (capi_dpstrf's range)");
+    if (!(args.pivot_rtol >= 0.0) || !(args.pivot_tol_scale >= 0.0) || !(args.pivot_rtol <= 1.0e150) || !(args.pivot_tol_scale <= 1.0e150))
+      throw std::invalid_argument("qr::cacqr::factor_pivoted: pivot_rtol and pivot_tol_scale must be finite and >= 0");
+    capi_handle_t h = capital::handle();
+    args.factored = false;
+    args.pivoted = false;
+    args.rank = 0;
+    args.piv.clear();
+    args.Q._register_(n, m_glob, CommInfo.c, CommInfo.d);
+    args.G._register_(n, n, 1, 1);
+    args.Ginv._register_(n, n, 1, 1);
+    args.R1._register_(n, n, 1, 1);
+    args.Rp._register_(n, n, 1, 1);
+    args.Piv._register_(1, (n + 1) / 2, 1, 1);
+    if (SP::packed_gram) args.Gpacked._register_(n, n, 1, 1);
+    int* const piv = reinterpret_cast<int*>(args.Piv.data());
+    CAPITAL_CHECK(capi_reset_info(h));
+    args.potrf_info = 0;
+    args.sweep_shift.clear(); args.sweep_trace.clear(); args.sweep_cond_bound.clear();
+    CRITTER_START(CQR::gram);
+    CAPITAL_CHECK(capi_dsyrk(h, CAPI_UPPER, CAPI_TRANS, n, m_loc, 1.0, A.data(), m_loc, 0.0, args.G.data(), n));       // K7
+    if (CommInfo.size > 1) {                                                                                       // C8
+      if (SP::packed_gram) {
+        serialize<uppertri, uppertri>::invoke(args.G, args.Gpacked, 0, n, 0, n, 0, n, 0, n);
+        CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, args.Gpacked.data(), args.Gpacked.num_elems()));
+        serialize<uppertri, uppertri>::invoke(args.Gpacked, args.G, 0, n, 0, n, 0, n, 0, n);
+      } else {
+        CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, args.G.data(), n * n));
+      }
+    }
+    CRITTER_STOP(CQR::gram);
+    CRITTER_START(CQR::formR);
+    // the factor of a shifted sweep's shift, or the user's tolerance squared (G holds squared norms)
+    const double floor_tol = 11.0 * ((double)m_glob * (double)n + (double)n * (double)(n + 1)) * 0x1p-53;
+    const double tol = args.pivot_tol_scale * std::max(args.pivot_rtol * args.pivot_rtol, floor_tol);
+    args.pivot_tol = tol;
+    int rank = 0;
+    CAPITAL_CHECK(capi_dpstrf(h, n, args.G.data(), n, tol, piv, &rank));                                              // identical bits on every rank
+    args.rank = rank;
+    args.piv.resize((size_t)n);
+    CAPITAL_CHECK(capi_memcpy_d2h(h, args.piv.data(), piv, sizeof(int) * (size_t)n));
+    if (rank < 1) {
+      CRITTER_STOP(CQR::formR);
+      throw std::domain_error("cacqr::factor_pivoted: numerical rank 0: no diagonal entry of the Gram matrix exceeds tol * trace (A is zero or not finite)");
+    }
+    const int64_t k = rank;
+    // M = P(:, 0:k) R11^-1 (n x k) in R1; Q1 = A M
+    CAPITAL_CHECK(capi_dlacpy(h, 1, k, k, args.G.data(), n, args.Ginv.data(), n));
+    CAPITAL_CHECK(capi_dtrtri(h, CAPI_UPPER, CAPI_NONUNIT, k, args.Ginv.data(), n));
+    CAPITAL_CHECK(capi_drow_scatter(h, 1, k, k, n, args.Ginv.data(), n, piv, args.R1.data(), n));
+    CAPITAL_CHECK(capi_dgemm(h, CAPI_NOTRANS, CAPI_NOTRANS, m_loc, k, n, 1.0, A.data(), m_loc, args.R1.data(), n, 0.0, args.Q.data(), m_loc));
+    CRITTER_STOP(CQR::formR);
+    {
+      // one plain sweep on the m_loc x k panel: sweep_1d works on args.G / Ginv / Gpacked as blocks of the panel's own order, so k x k blocks stand in
+      // for them while it runs; [R11 R12] stays where capi_dpstrf left it
+      matrix<double, Dim, rect> Gk(k, k, 1, 1), Gik(k, k, 1, 1);
+      matrix<double, Dim, uppertri> Gpk;
+      if (SP::packed_gram) Gpk._register_(k, k, 1, 1);
+      std::swap(args.G, Gk); std::swap(args.Ginv, Gik); std::swap(args.Gpacked, Gpk);
+      try {
+        sweep_1d(args.Q.data(), args.Q.scratch(), m_loc, k, args, CommInfo);
+      } catch (...) {
+        std::swap(args.G, Gk); std::swap(args.Ginv, Gik); std::swap(args.Gpacked, Gpk);
+        throw;
+      }
+      std::swap(args.G, Gk); std::swap(args.Ginv, Gik); std::swap(args.Gpacked, Gpk);
+      args.Q.swap();
+      // Rp(0:k, :) = R2 [R11 R12]: the leading block's strictly lower part was never written
+      CAPITAL_CHECK(capi_dtrizero(h, CAPI_UPPER, k, args.G.data(), n));
+      CAPITAL_CHECK(capi_memset_async(h, args.Rp.data(), 0, sizeof(double) * (size_t)(n * n)));
+      CAPITAL_CHECK(capi_dtrmm_oop(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, k, n, 1.0, Gk.data(), k, args.G.data(), n, args.Rp.data(), n));
+      CAPITAL_CHECK(capi_get_info(h, &args.potrf_info));                                                              // drains the stream: the k x k blocks may go
+    }
+    if (!IP::keep_work) { args.G._destroy_(); args.Ginv._destroy_(); args.R1._destroy_(); args.Gpacked._destroy_(); }
+    if (args.potrf_info != 0)
+      throw std::domain_error("cacqr::factor_pivoted: the Gram matrix of the rank-" + std::to_string(k) + " panel is not positive definite (pivot " +
+                              std::to_string(args.potrf_info) + "): Q and R are not valid; a larger pivot_tol_scale drops more columns");
+    args.factored = true;
+    args.pivoted = true;
+  }
+
   // min ||A X - B||_F on the factors factor(A, args, CommInfo) left: args.X (n x r) and, with `residual`, args.ls_residual_norms.
   // B is distributed exactly as A: matrix<double, int64_t, rect>(r, m, c, d), the same row-cyclic owner map.  See the file comment.
   template <typename MatrixType, typename ArgType, typename CommType>
@@ -135,6 +256,7 @@ public:
     if (CommInfo.c != 1) throw std::logic_error("qr::cacqr::least_squares is built for the 1-D variant (c == 1) only");
     if (!&capi_dgemtn_ts || !&capi_dresid_ts)
       throw std::logic_error("qr::cacqr: this C-ABI library has no capi_dgemtn_ts / capi_dresid_ts: no least-squares solve");
+    if (args.pivoted) { least_squares_pivoted(A, B, args, CommInfo, residual); return; }
     if (!args.factored || args.potrf_info != 0 || !args.Q.filled() || !args.R.filled())
       throw std::logic_error("qr::cacqr::least_squares: factor() has not run or did not succeed: there is no valid Q and R to solve with");
     capi_handle_t h = capital::handle();
@@ -181,6 +303,7 @@ public:
   static void svd(ArgType& args, CommType&& CommInfo, bool left = true) {
     if (CommInfo.c != 1) throw std::logic_error("qr::cacqr::svd is built for the 1-D variant (c == 1) only");
     if (!&capi_dgesvj) throw std::logic_error("qr::cacqr: this C-ABI library has no capi_dgesvj: no singular value decomposition");
+    if (args.pivoted) throw std::logic_error("qr::cacqr::svd: the resident factors are factor_pivoted's (a trapezoidal R): svd is built for factor()'s pair only");
     if (!args.factored || args.potrf_info != 0 || !args.Q.filled() || !args.R.filled())
       throw std::logic_error("qr::cacqr::svd: factor() has not run or did not succeed: there is no valid Q and R to decompose");
     capi_handle_t h = capital::handle();
@@ -222,6 +345,46 @@ public:
   }
 
 protected:
+  // least_squares on factor_pivoted's factors: the basic solution X = P [R11^-1 (Q^T B); 0] -- C = Q^T B (k x r, the kernel choice of the plain
+  // path at width k) and its all-reduce, Y = R11^-1 C by capi_dtrsm on Rp's leading block, X by capi_drow_scatter, residual norms on A as there
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void least_squares_pivoted(const MatrixType& A, const MatrixType& B, ArgType& args, CommType&& CommInfo, bool residual) {
+    if (!&capi_drow_scatter) throw std::logic_error("qr::cacqr: this C-ABI library has no capi_drow_scatter: no solve on pivoted factors");
+    if (!args.factored || args.potrf_info != 0 || !args.Q.filled() || !args.Rp.filled() || !args.Piv.filled() || args.rank < 1)
+      throw std::logic_error("qr::cacqr::least_squares: factor_pivoted() did not succeed: there is no valid Q and R to solve with");
+    capi_handle_t h = capital::handle();
+    const int64_t n = A.num_columns_global(), m_loc = A.num_rows_local(), r = B.num_columns_global(), k = args.rank;
+    if (r < 1 || B.num_rows_local() != m_loc || B.num_rows_global() != A.num_rows_global() || args.Q.num_rows_local() != m_loc ||
+        args.Q.num_columns_global() != n || k > n)
+      throw std::invalid_argument("qr::cacqr::least_squares: B must have r >= 1 columns and A's rows, distributed as A, and A must be the factored matrix");
+    CRITTER_START(CQR::lstsq);
+    if (args.X.filled() && args.X.num_columns_local() != r) args.X._destroy_();
+    args.X._register_(r, n, 1, 1);
+    double* const Y = args.X.scratch();                                                                             // n x r; rows >= k stay zero
+    const int64_t W = CAPI_TS_MAX_RHS;
+    const bool by_gemm = k >= 256 && m_loc >= 64 * k;
+    for (int64_t j = 0; j < r; j += W) {
+      const int64_t rb = std::min(W, r - j);
+      if (by_gemm) CAPITAL_CHECK(capi_dgemm(h, CAPI_TRANS, CAPI_NOTRANS, k, rb, m_loc, 1.0, args.Q.data(), m_loc, B.data() + j * m_loc, m_loc, 0.0, Y + j * n, n));
+      else CAPITAL_CHECK(capi_dgemtn_ts(h, m_loc, k, rb, 1.0, args.Q.data(), m_loc, B.data() + j * m_loc, m_loc, 0.0, Y + j * n, n));
+    }
+    if (CommInfo.size > 1) CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, Y, n * r));
+    CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, k, r, 1.0, args.Rp.data(), n, Y, n));  // Y = R11^-1 C
+    CAPITAL_CHECK(capi_drow_scatter(h, 0, k, r, n, Y, n, reinterpret_cast<const int*>(args.Piv.data()), args.X.data(), n));
+    args.ls_residual_norms.clear();
+    if (residual) {
+      if (args.LsNorm2.filled() && args.LsNorm2.num_columns_local() != r) args.LsNorm2._destroy_();
+      args.LsNorm2._register_(r, 1, 1, 1);
+      for (int64_t j = 0; j < r; j += W)
+        CAPITAL_CHECK(capi_dresid_ts(h, m_loc, n, std::min(W, r - j), A.data(), m_loc, args.X.data() + j * n, n, B.data() + j * m_loc, m_loc, nullptr, 0,
+                                     args.LsNorm2.data() + j));
+      if (CommInfo.size > 1) CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, args.LsNorm2.data(), r));
+      args.ls_residual_norms = args.LsNorm2.to_host();
+      for (double& v : args.ls_residual_norms) v = std::sqrt(v);
+    }
+    CRITTER_STOP(CQR::lstsq);
+  }
+
   // one CholeskyQR sweep: dst <- src * chol(src^T src)^-1 ; leaves R in args.G and R^-1 in args.Ginv
   // src_tiled / dst_tiled: the panel is a "panel32" image (include/capital_hip.h) instead of column-major -- the intermediate panels Q1, Q2, ..
   // rec != nullptr (runs with num_shifted > 0): the sweep's 4-double device record; shifted: equilibrate and shift the Gram matrix (m_glob rows)
@@ -262,6 +425,7 @@ protected:
     if (SP::packed_gram) args.Gpacked._register_(n, n, 1, 1);
     CAPITAL_CHECK(capi_reset_info(h));
     args.potrf_info = 0;
+    args.pivoted = false;                // the factors about to be written are factor()'s
     const int64_t sweeps = std::max<int64_t>(1, (int64_t)args.num_iter), shifted = (int64_t)args.num_shifted;
     if (sweeps > 4 || shifted > sweeps) throw std::invalid_argument("qr::cacqr: num_iter is 1..4 sweeps, of which num_shifted <= num_iter are shifted");
     double* rec = nullptr;               // device records, 4 doubles per sweep (runs with shifted sweeps only)

@@ -242,6 +242,31 @@ int capi_dlacn_block(capi_handle_t h, int init, int64_t n, int64_t r, double* X,
  * Workspace, of the handle's own: n x n doubles (2 n x n with U) and 2 n more. */
 int capi_dgesvj(capi_handle_t h, int64_t n, const double* R, int64_t ldr, double* U, int64_t ldu, double* sigma, double* V, int64_t ldv,
                 int* sweeps_host);
+/* ---- Cholesky with complete pivoting of a Gram matrix (LAPACK's dpstrf, upper): the rank-revealing step of a column-pivoted CholeskyQR
+ * (qr::cacqr::factor_pivoted: it takes capi_dpotrf_trtri's place in the first sweep and stops where the remaining columns are noise).
+ * Not in the reference: cacqr.hpp stops at Q and R.  G is n x n, column-major, ldg >= n, 1 <= n <= 2048; anything else, a null pointer or a tol that
+ * is not >= 0 returns CAPI_EINVAL with nothing touched, *rank_host included.  Only G's upper triangle, diagonal included, is read or written: what
+ * lies below may be NaN and influences nothing.  On exit rows 0 .. k - 1 of the triangle hold the k x n upper trapezoid R = [R11 R12] with
+ * P^T G P = R^T R + diag-block(0, S), S the (n - k) x (n - k) Schur complement; rows >= k of the triangle are unspecified.  piv (DEVICE, n ints,
+ * 0-based) is always a full permutation: column j of the permuted matrix is column piv[j] of G.  *rank_host = k; reading it is the call's single
+ * stream synchronisation (as sweeps_host in capi_dgesvj) and the only host traffic.  The handle's info word is not touched.
+ * Stopping rule: thresh = tol * trace(G), the trace over the input diagonal, summed by one workgroup in a fixed order.  At step j, p is the FIRST
+ * index of the largest remaining (Schur-updated) diagonal entry d_p; the factorization stops at rank j unless d_p > thresh -- written so that a NaN
+ * compares false and stops.  tol = 0 factors until a pivot is <= 0.  Non-finite input still ends the call (every loop has a trip count fixed by n)
+ * with 0 <= k <= n and piv a permutation; the values are then unspecified.
+ * Method: dpstrf's blocked, lazy scheme, panels of 32 columns, one workgroup (up to 1024 threads) per panel -- updated diagonal, argmax, the
+ * symmetric swap in upper storage, the swap of the rows of R already computed, the panel's row of R -- and G22 -= R_strip^T R_strip through
+ * capi_dsyrk.  All ceil(n / 32) rounds are enqueued without a host round trip: a stop sets a device flag, the panel kernel zeroes its unfinished
+ * strip rows, later panel kernels read the flag at entry and return.  Steps are ordered by kernel boundaries on the handle's stream: no
+ * cooperative launch, no device-side waiting, no atomics; sums have a fixed order, so every result is bit-identical from run to run and on every
+ * device that holds the same G -- the ranks of a 1-D grid agree on piv without communication.  Pointers aligned to 8 bytes (piv to 4).
+ * Workspace, of the handle's own: 16 bytes, and capi_dsyrk's. */
+int capi_dpstrf(capi_handle_t h, int64_t n, double* G, int64_t ldg, double tol, int* piv, int* rank_host);
+/* The permutation as a kernel: D (n x ncols, ldd >= n) <- 0, then D(piv[i], :) <- S(i, :) for i < k (0 <= k <= n; S k x ncols, lds >= k; piv DEVICE
+ * ints of which the first k are read, distinct and in 0 .. n - 1: an index outside that range writes nothing).  Not in the reference: cacqr.hpp stops
+ * at Q and R.  tri = 1 takes only S's upper triangle: entries below the diagonal count as zero and are not read.  Serves M = P(:, 0:k) R11^-1 and the
+ * basic least-squares solution X = P [Y; 0].  D must not alias S.  k == 0: zeros alone; n == 0 or ncols == 0: nothing.  No workspace. */
+int capi_drow_scatter(capi_handle_t h, int tri, int64_t k, int64_t ncols, int64_t n, const double* S, int64_t lds, const int* piv, double* D, int64_t ldd);
 /* LAPACKE_dgeqrf / LAPACKE_dorgqr behind lapack::engine::_geqrf / _orgqr (lapack/interface.hpp:60-88; the reference has
  * the slots but no caller -- CholeskyQR2 is its QR).  Householder QR, LAPACK storage: R in the upper triangle, the
  * reflectors v_j (unit first entry implied) below it, tau[min(m,n)] on the DEVICE.  capi_dorgqr overwrites A (m x n,
