@@ -41,6 +41,8 @@ _SIGS = {
     "capi_dresid_ts": [_i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
     "capi_dtrmm_thin": [_int, _int, _i64, _i64, _i64, _dbl, _vp, _i64, _i64, _vp, _i64, _dbl, _vp, _i64],
     "capi_dtrsm_thin": [_int, _i64, _i64, _vp, _i64, _i64, _vp, _i64],
+    "capi_dchud": [_int, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, C.POINTER(_int)],
+    "capi_dchud_inv": [_int, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64],
     "capi_dresid_sym": [_i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
     "capi_dsym_abs": [_i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
     "capi_dberr": [_i64, _i64, _vp, _i64, _vp, _i64, _vp],
@@ -148,6 +150,8 @@ def load():
     L.capi_device_count.restype = _int
     L.capi_dlacn_state_bytes.argtypes = [_i64, _i64]
     L.capi_dlacn_state_bytes.restype = C.c_size_t
+    L.capi_dchud_log_bytes.argtypes = [_i64, _i64]
+    L.capi_dchud_log_bytes.restype = C.c_size_t
     _lib = L
     return L
 

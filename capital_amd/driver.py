@@ -60,6 +60,7 @@ def bind(D):
     D.capital_cholinv_rcond_applies.argtypes = [_vp, _dp, _dp, C.POINTER(_int)]
     D.capital_cholinv_error_bounds.argtypes = [_vp, _i64, _dp, _dp, _dp]
     D.capital_cholinv_solve_expert.argtypes = [_vp, _i64, _dp, _dp, _dp, _int, _dp, _dp]
+    D.capital_cholinv_update.argtypes = [_vp, _i64, _dp, _int]
     D.capital_cacqr_create.argtypes = [_i64, _i64] + [_int] * 8
     D.capital_cacqr_create.restype = _vp
     D.capital_cacqr_set_A.argtypes = [_vp, _dp]
@@ -226,6 +227,18 @@ class Cholinv:
         _ck(self.D.capital_cholinv_solve_expert(self.p, r, b.ctypes.data_as(_dp), X.ctypes.data_as(_dp), res.ctypes.data_as(_dp) if residual else None,
                                                 int(refine), ferr.ctypes.data_as(_dp), berr.ctypes.data_as(_dp)), "solve_expert")
         return X, res, ferr, berr
+
+    def update(self, V, downdate=False):
+        """A <- A + V V^T (downdate=True: A - V V^T) on the factors of the last factor(), without a new factorisation (cholesky::cholinv::update, one
+        rank): R, R^-1 where one exists and A's upper triangle are updated on the device in O(n^2 r).  V: n x r, any r >= 1 (blocks of 32 columns).
+        Every form of solve(), rcond() and solve_expert() then works on the updated matrix.  Raises DriverError when a downdate leaves the matrix not
+        positive definite: A is then unchanged, and solve() refuses until the next factor()."""
+        v = np.asfortranarray(V, dtype=np.float64)
+        if v.ndim == 1:
+            v = np.asfortranarray(v[:, None])
+        if v.ndim != 2 or v.shape[0] != self.n or v.shape[1] < 1:
+            raise DriverError(f"Cholinv.update: V must be {self.n} x r with r >= 1, got {v.shape}")
+        _ck(self.D.capital_cholinv_update(self.p, v.shape[1], v.ctypes.data_as(_dp), -1 if downdate else 1), "update")
 
     def _get(self, which):
         out = np.zeros((self.n_loc, self.n_loc), order="F")

@@ -42,6 +42,7 @@ struct cholinv_problem {
   virtual void solve(int64_t r, const double* B_host, double* X_host, double* resnorm_host, int refine) = 0;
   virtual void rcond(double* rcond, double* anorm1, int* applies) = 0;
   virtual void error_bounds(int64_t r, const double* B_host, double* ferr_host, double* berr_host, int* applies) = 0;
+  virtual void update(int64_t r, const double* V_host, int sign) = 0;
 };
 
 template <class Alg>
@@ -108,6 +109,13 @@ struct cholinv_impl : cholinv_problem {
     std::memcpy(ferr_host, pack.solve_ferr.data(), sizeof(double) * (size_t)r);
     std::memcpy(berr_host, pack.solve_berr.data(), sizeof(double) * (size_t)r);
     if (applies) *applies = pack.lacn_applies;
+  }
+  // A <- A + sign V V^T on the factors of the last factor(): V_host n x r column-major
+  void update(int64_t r, const double* V_host, int sign) override {
+    if (r < 1 || !V_host) throw std::invalid_argument("cholinv update: r >= 1 columns and V expected");
+    MatrixType V(r, A.num_rows_global(), 1, 1);
+    V.from_host(V_host);
+    Alg::update(A, V, pack, grid, sign);
   }
 };
 
@@ -328,6 +336,12 @@ int capital_cholinv_solve_expert(void* p, int64_t r, const double* B_host, doubl
     ((cholinv_problem*)p)->solve(r, B_host, X_host, resnorm_host_or_null, refine);
     ((cholinv_problem*)p)->error_bounds(r, B_host, ferr_host, berr_host, nullptr);
   });
+}
+// A <- A + sign V V^T (sign = +1 update, -1 downdate) WITHOUT a new factorisation (cholesky::cholinv::update; one rank, after capital_cholinv_factor):
+// V_host n x r column-major, any r >= 1.  R, R^-1 where one exists, and A's upper triangle are updated on the device.  -1 with the failing step in
+// capital_drv_last_error when a downdate leaves the matrix not positive definite: A is then unchanged and the factors are invalid until the next factor.
+int capital_cholinv_update(void* p, int64_t r, const double* V_host, int sign) {
+  return guarded([&] { ((cholinv_problem*)p)->update(r, V_host, sign); });
 }
 int capital_cholinv_destroy(void* p) { return guarded([&] { capital::sync(); delete (cholinv_problem*)p; }); }
 

@@ -33,6 +33,10 @@
 #pragma weak capi_dcolamax
 #pragma weak capi_dlacn_block
 #pragma weak capi_dlacn_state_bytes
+// .. and the rank-r update of the factors: without them update() refuses and everything else runs as before
+#pragma weak capi_dchud
+#pragma weak capi_dchud_inv
+#pragma weak capi_dchud_log_bytes
 
 namespace cholesky {
 
@@ -101,6 +105,9 @@ public:
     int lacn_applies = 0;
     std::vector<double> solve_ferr, solve_berr;
     matrix<ScalarType, DimensionType, rect> BoundsRho, BoundsWt, BoundsV1, BoundsV2, BoundsState, BoundsSmall;
+    // update(): the scratch copy of a block of V (n x CAPI_TS_MAX_RHS) and the log of its steps; the step of the last failed downdate (0: none)
+    matrix<ScalarType, DimensionType, rect> UpdV, UpdLog;
+    int update_info = 0;
   };
 
   template <typename MatrixType, typename ArgType, typename CommType>
@@ -384,6 +391,77 @@ public:
     }
     release_bounds_work(args);
     CRITTER_STOP(CI::error_bounds);
+  }
+
+  // A <- A + sign V V^T (sign = +1: update, -1: downdate) on the factors factor(A, args, CommInfo) left, WITHOUT a new factorisation: O(n^2 r) instead
+  // of O(n^3) (LINPACK's dchud / dchdd; ONE rank, solve()'s preconditions).  V: matrix<double, int64_t, rect>(r, n, 1, 1), any r >= 1; it is processed
+  // in blocks of CAPI_TS_MAX_RHS columns from a scratch copy and is not modified.  Per block:
+  //   1. R <- R' with R'^T R' = R^T R + sign V_b V_b^T (capi_dchud: n dependent steps in panels of 32 rows, each step logged)
+  //   2. the info word of the block is read (the call's only synchronisation)
+  //   3. R^-1 <- R'^-1 from the log (capi_dchud_inv), where an inverse exists: not in TRSM mode; with complete_inv == 0 and a top split at h1 the two
+  //      diagonal blocks take the step ranges [0, h1) and [h1, n) and the unformed R^-1_12 is not touched
+  // and at the end A's upper triangle takes sign V V^T (capi_dsyrk), so that solve()'s refinement, condition() and error_bounds() see the updated matrix.
+  // Every resident image of the factors ends up consistent: with Serialize and SaveIntermediates the full-storage working images are updated and packed
+  // again (serialize); with FlushIntermediates, which keeps no full image, the packed triangles are updated in place; NoSerialize has one image.
+  // A downdate that leaves the matrix not positive definite: A is exactly as it was, args.factored = false (solve() reports that there are no valid
+  // factors until the next factor()), args.update_info is the failing step (1-based, within its block of columns) and std::domain_error is thrown.
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void update(MatrixType& A, const MatrixType& V, ArgType& args, CommType&& CommInfo, int sign = 1) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::update takes rect-structured A and V");
+    require_factors(args, CommInfo, "cholinv::update");
+    if (!&capi_dchud || !&capi_dchud_inv || !&capi_dchud_log_bytes) throw std::logic_error("cholinv: this C-ABI library has no capi_dchud / capi_dchud_inv: no update of the factors");
+    const int64_t n = args.localDimension, r = V.num_columns_global();
+    if (r < 1 || V.num_rows_global() != n || V.num_rows_local() != n || A.num_rows_local() != n || A.num_columns_local() != n || (sign != 1 && sign != -1))
+      throw std::invalid_argument("cholinv::update: V must be n x r with r >= 1 (matrix(r, n, 1, 1)), A the factored matrix, sign +1 or -1");
+    args.update_info = 0;
+    if (n == 0) return;
+    CRITTER_START(CI::update);
+    constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    const int64_t W = CAPI_TS_MAX_RHS, h1 = args.top_split;
+    const bool inverse = !args.solve_with_trsm;
+    const bool blocks = inverse && !args.complete_inv && h1 > 0 && h1 < n;
+    // the image that takes the steps: the full-storage working image where one is resident (never one that FlushIntermediates released), else the
+    // packed triangle in place; NoSerialize: the rect structure itself
+    const bool viaR = packed && IP::keep_arena && args.Rfull.filled(), viaI = packed && inverse && IP::keep_arena && args.Rinvfull.filled();
+    double* const Rp = viaR ? args.Rfull.data() : (double*)args.R.data();
+    double* const Ip = !inverse ? nullptr : (viaI ? args.Rinvfull.data() : (double*)args.Rinv.data());
+    const int64_t ldR = (viaR || !packed) ? n : 0, ldI = (viaI || !packed) ? n : 0;
+    args.UpdV._register_(W, n, 1, 1);
+    args.UpdLog._register_((int64_t)((capi_dchud_log_bytes(n, W) + 7) / 8), 1, 1, 1);
+    int info = 0;
+    int64_t bad_block = 0;
+    for (int64_t j = 0; j < r && info == 0; j += W) {
+      const int64_t rb = std::min(W, r - j);
+      CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, V.data() + j * n, n, args.UpdV.data(), n));
+      CAPITAL_CHECK(capi_dchud(h, sign, n, rb, Rp, ldR, 0, args.UpdV.data(), n, args.UpdLog.data(), &info));
+      if (info != 0) { bad_block = j; break; }
+      if (!inverse) continue;
+      if (blocks) {
+        CAPITAL_CHECK(capi_dchud_inv(h, sign, n, rb, Ip, ldI, 0, args.UpdLog.data(), 0, h1));
+        CAPITAL_CHECK(capi_dchud_inv(h, sign, n, rb, Ip, ldI, 0, args.UpdLog.data(), h1, n));
+      } else {
+        CAPITAL_CHECK(capi_dchud_inv(h, sign, n, rb, Ip, ldI, 0, args.UpdLog.data(), 0, n));
+      }
+    }
+    if (info == 0) {
+      if (viaR) serialize<uppertri, uppertri>::invoke(args.Rfull, args.R, 0, n, 0, n, 0, n, 0, n);
+      if (viaI) serialize<uppertri, uppertri>::invoke(args.Rinvfull, args.Rinv, 0, n, 0, n, 0, n, 0, n);
+      CAPITAL_CHECK(capi_dsyrk(h, CAPI_UPPER, CAPI_NOTRANS, n, r, (double)sign, V.data(), n, 1.0, A.data(), n));
+    } else {
+      args.factored = false;
+      args.update_info = info;
+    }
+    if (!IP::keep_arena) {
+      capital::sync();
+      args.UpdV._destroy_(); args.UpdLog._destroy_();
+    }
+    CRITTER_STOP(CI::update);
+    if (info != 0)
+      throw std::domain_error("cholinv::update: the " + std::string(sign > 0 ? "updated" : "downdated") + " matrix is not positive definite (step " +
+                              std::to_string(info) + " of " + std::to_string(n) + (r > W ? ", columns from " + std::to_string(bad_block) + " of V" : std::string()) +
+                              "); A is unchanged, R and Rinv are not valid: factor() again");
   }
 
   // ---- TRSM mode -----------------------------------------------------------------------------------------------------------

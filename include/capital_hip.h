@@ -174,6 +174,34 @@ int capi_dtrmm_thin(capi_handle_t h, int shape, int trans, int64_t m, int64_t n,
  * the steps are ordered by kernel boundaries on the handle's stream, sums have a fixed order (bit-identical runs, no atomics).
  * Workspace: capi_dtrmm_thin's for the largest product, the top level's T12 (about n / 2 output lines), of the handle's workspace; none for n <= 512. */
 int capi_dtrsm_thin(capi_handle_t h, int trans, int64_t n, int64_t r, const double* T, int64_t ldt, int64_t col0, double* B, int64_t ldb);
+/* ---- the rank-r update (sign = +1) or downdate (sign = -1) of an upper triangular factor and of its inverse: T'^T T' = T^T T + sign V V^T in O(n^2 r),
+ * LINPACK's dchud / dchdd (cholesky::cholinv::update).  Not in the reference: cholinv.hpp stops at R and R^-1.  The conventions are those of the thin
+ * calls: device pointers, column-major, 1 <= r <= CAPI_TS_MAX_RHS and sign = +1 or -1 (else CAPI_EINVAL, nothing is touched), pointers aligned to 8 bytes;
+ * n == 0 is OK. ----
+ * capi_dchud: T is upper triangular of order n with a positive diagonal, addressed exactly as capi_dtrsm_thin addresses it: ldt >= n is column-major,
+ * ldt == 0 a diagonal sub-triangle of a PACKED upper triangle that starts at the triangle's column col0 (T points at the sub-triangle's first element;
+ * offsets are 64-bit).  V is n x r (ldv >= n) and is destroyed.  Nothing below T's diagonal is read or written: it may hold NaN, and zeros there stay zeros.
+ * Step k = 0 .. n - 1 has alpha = T_kk and x = the current row k of V: beta = sqrt(alpha^2 + sign ||x||^2); for every column j >= k
+ * t = (alpha T_kj + sign x^T v_j) / beta, v_j <- v_j - x (T_kj + t) / (alpha + beta), T_kj <- t (the two divisions as reciprocals, taken once per step).
+ * `log` is DEVICE memory of capi_dchud_log_bytes(n, r) bytes (0 for arguments out of range): per step the r + 2 doubles x_k, alpha_k, beta_k, for
+ * capi_dchud_inv.  *info_host = 0 on success, or the 1-based step at which alpha^2 + sign ||x||^2 > 0 did not hold (written so that a NaN compares
+ * false): a downdate that leaves the matrix not positive definite.  T is then unspecified from that row down and the status is still CAPI_OK; the stop
+ * sets a device flag, later kernels of the call read it at entry and return (as in capi_dpstrf).  Reading *info_host is the call's single stream
+ * synchronisation and the only host traffic; the handle's info word is not touched.
+ * Method (csrc/chud_plan.h): panels of 32 rows; per panel one workgroup runs the 32 dependent steps on the diagonal block and writes the log, then a
+ * wide kernel gives every trailing column a thread (v_j in registers, T through an LDS tile): 2 ceil(n / 32) - 1 launches, ordered by kernel boundaries
+ * on the handle's stream: no cooperative launch, no device-side waiting, no atomics; sums have a fixed order (bit-identical runs).  T is read and
+ * written once.  Workspace, of the handle's own: 8 bytes. */
+size_t capi_dchud_log_bytes(int64_t n, int64_t r);
+int capi_dchud(capi_handle_t h, int sign, int64_t n, int64_t r, double* T, int64_t ldt, int64_t col0, double* V, int64_t ldv, double* log,
+               int* info_host);
+/* capi_dchud_inv: the logged steps k0 <= k < k1 of a capi_dchud(sign, n, r, ..) applied to the rows of the upper triangular Tinv (order n, addressed as T
+ * there) that belong to the diagonal sub-triangle [k0, k1): with Tinv = T^-1 before, that sub-triangle is the inverse of T' 's afterwards (k0 = 0,
+ * k1 = n: Tinv <- T'^-1).  Not in the reference: cholinv.hpp stops at R and R^-1.  The step of capi_dchud on the pairs (Tinv_ck, e_c), c <= k, e_c an
+ * r-vector that starts at zero and is dropped.  Nothing outside the sub-triangle is read or written: for a factor whose inverse is kept as two
+ * diagonal blocks (cholinv with complete_inv == 0) the ranges [0, h1) and [h1, n) update the blocks and leave the unformed block alone.  One launch,
+ * a thread per row: no chain, no synchronisation, no workspace; the same bits on every run.  0 <= k0 <= k1 <= n; k0 == k1 does nothing. */
+int capi_dchud_inv(capi_handle_t h, int sign, int64_t n, int64_t r, double* Tinv, int64_t ldt, int64_t col0, const double* log, int64_t k0, int64_t k1);
 /* capi_dresid_sym: Rout (n x r) <- B - S X and colnorm2[j] <- sum_i Rout(i, j)^2 (DEVICE, r doubles) for the SYMMETRIC S whose upper triangle, diagonal
  * included, is that of the column-major A (lda >= n): the residual of cholesky::cholinv::solve.  Not in the reference: cholinv.hpp stops at R and R^-1.
  * NO element below A's diagonal influences any output: it may hold NaN, Inf or garbage (inside the tiles that the diagonal crosses the unwanted
