@@ -27,6 +27,12 @@ using T = double;
 using U = int64_t;
 using MatrixType = matrix<T, U, rect>;
 
+// the local block of M, as it lies on the device, into host memory
+template <class M>
+void fetch(const M& m, double* host) {
+  CAPITAL_CHECK(capi_memcpy_d2h(capital::handle(), host, m.data(), sizeof(double) * (size_t)m.num_elems()));
+}
+
 struct cholinv_problem {
   virtual ~cholinv_problem() {}
   virtual void generate() = 0;
@@ -57,10 +63,8 @@ struct cholinv_impl : cholinv_problem {
   void factor() override { Alg::factor(A, pack, grid); }
   double residual() override { return cholesky::validate<Alg>::residual(A, pack, grid); }
   void get(int which, double* host) override {
-    if (which == 0) { auto v = A.to_host(); std::memcpy(host, v.data(), sizeof(double) * v.size()); return; }
-    auto M = which == 1 ? Alg::construct_R(pack, grid) : Alg::construct_Rinv(pack, grid);
-    auto v = M.to_host();
-    std::memcpy(host, v.data(), sizeof(double) * v.size());
+    if (which == 0) { fetch(A, host); return; }
+    fetch(which == 1 ? Alg::construct_R(pack, grid) : Alg::construct_Rinv(pack, grid), host);
   }
   // local rows rows[0..count) of R (which = 1) or R^-1 (2), column-major count x n_loc: a sample of a factor that is too large
   // to fetch whole (n = 65536 on one GPU: 32 GiB)
@@ -89,8 +93,7 @@ struct cholinv_impl : cholinv_problem {
     MatrixType B(r, A.num_rows_global(), 1, 1);
     B.from_host(B_host);
     Alg::solve(A, B, pack, grid, refine, resnorm_host != nullptr);
-    auto x = pack.X.to_host();
-    std::memcpy(X_host, x.data(), sizeof(double) * x.size());
+    fetch(pack.X, X_host);
     if (resnorm_host) std::memcpy(resnorm_host, pack.solve_residual_norms.data(), sizeof(double) * (size_t)r);
   }
   void rcond(double* rcond, double* anorm1, int* applies) override {
@@ -179,8 +182,7 @@ struct cacqr_impl : cacqr_problem {
     MatrixType B(r, A.num_rows_global(), grid.c, grid.d);
     B.from_host(B_host);
     Alg::least_squares(A, B, pack, grid, resnorm_host != nullptr);
-    auto x = pack.X.to_host();
-    std::memcpy(X_host, x.data(), sizeof(double) * x.size());
+    fetch(pack.X, X_host);
     if (resnorm_host) std::memcpy(resnorm_host, pack.ls_residual_norms.data(), sizeof(double) * (size_t)r);
   }
   // A = U diag(s) V^T on the factors of the last factor(): s_host receives the n singular values (descending), V_host (may be NULL) the n x n V,
@@ -189,8 +191,8 @@ struct cacqr_impl : cacqr_problem {
     if (!s_host || (want_left && !U_host)) throw std::invalid_argument("cacqr svd: a place for the singular values, and for U with want_left, expected");
     Alg::svd(pack, grid, want_left);
     std::memcpy(s_host, pack.singular_values.data(), sizeof(double) * pack.singular_values.size());
-    if (V_host) { auto v = pack.V.to_host(); std::memcpy(V_host, v.data(), sizeof(double) * v.size()); }
-    if (want_left) { auto u = pack.U.to_host(); std::memcpy(U_host, u.data(), sizeof(double) * u.size()); }
+    if (V_host) fetch(pack.V, V_host);
+    if (want_left) fetch(pack.U, U_host);
     if (sweeps) *sweeps = pack.svd_sweeps;
   }
   // column-pivoted CholeskyQR (qr::cacqr::factor_pivoted): rtol = the user's tolerance relative to ||A||_F (0: the floor alone), tol_scale multiplies
@@ -218,24 +220,21 @@ struct cacqr_impl : cacqr_problem {
   double residual() override { plain_factors_only("residual"); return qr::validate<Alg>::residual(A, pack, grid); }
   double orthogonality() override { plain_factors_only("orthogonality"); return qr::validate<Alg>::orthogonality(A, pack, grid); }
   void get(int which, double* host) override {
-    if (which == 0) { auto v = A.to_host(); std::memcpy(host, v.data(), sizeof(double) * v.size()); return; }
+    if (which == 0) { fetch(A, host); return; }
     if (which == 2 || which == 3) plain_factors_only("get");
-    if (which == 1) { auto v = Alg::construct_Q(pack, grid).to_host(); std::memcpy(host, v.data(), sizeof(double) * v.size()); return; }
+    if (which == 1) { fetch(Alg::construct_Q(pack, grid), host); return; }
     if (which == 3) {                                     // Q^T Q (summed over the ranks), n x n
       matrix<double, int64_t, rect> I(A.num_columns_global(), A.num_columns_global(), 1, 1);
       qr::validate<Alg>::gram_of_Q(pack, grid, I);
-      auto v = I.to_host();
-      std::memcpy(host, v.data(), sizeof(double) * v.size());
+      fetch(I, host);
       return;
     }
     if (which == 4) {                                     // Rp of factor_pivoted, n x n: rows < rank hold R, the rest is zero
       if (!pack.pivoted || !pack.Rp.filled()) throw std::invalid_argument("cacqr get: which = 4 (Rp) needs a successful factor_pivoted");
-      auto v = pack.Rp.to_host();
-      std::memcpy(host, v.data(), sizeof(double) * v.size());
+      fetch(pack.Rp, host);
       return;
     }
-    auto v = Alg::construct_R(pack, grid).to_host();
-    std::memcpy(host, v.data(), sizeof(double) * v.size());
+    fetch(Alg::construct_R(pack, grid), host);
   }
   void dims(int64_t* mloc, int64_t* n) override { *mloc = A.num_rows_local(); *n = A.num_columns_local(); }
   // local rows [row0, row0 + nrows) of A (which = 0) or Q (1), column-major nrows x n: a bounded window of a panel that is

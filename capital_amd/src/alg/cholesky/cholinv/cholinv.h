@@ -95,18 +95,19 @@ public:
     // of the recursion split (0: it did not).  With complete_inv == 0 that is where R^-1 has its unformed block R^-1_12.
     bool factored = false, factored_trsm = false;     // factored_trsm: the mode (solve_with_trsm) that factor() ran in
     DimensionType top_split = 0;
-    // the solution X (n x r) and, when asked for, ||b_j - A x_j||_2 per right-hand side; n x CAPI_TS_MAX_RHS work blocks
-    matrix<ScalarType, DimensionType, rect> X, SolveW1, SolveW2, SolveRho, SolveD, SolveNorm2;
+    // the solution X (n x r) and, when asked for, ||b_j - A x_j||_2 per right-hand side
+    matrix<ScalarType, DimensionType, rect> X, SolveNorm2;
     std::vector<double> solve_residual_norms;
     // condition(): ||A||_1, the reciprocal condition number 1 / (||A||_1 est ||A^-1||_1) as dpocon returns it, and the products with A^-1 that the
     // estimate took (at most 11).  error_bounds(): per column of X the componentwise backward error and the forward bound of dporfs, and the
-    // products its slowest block of columns took.  The work blocks of both: n x CAPI_TS_MAX_RHS each, the estimator's state, a few small results
+    // products its slowest block of columns took
     double anorm1 = 0.0, rcond = 0.0;
     int lacn_applies = 0;
     std::vector<double> solve_ferr, solve_berr;
-    matrix<ScalarType, DimensionType, rect> BoundsRho, BoundsWt, BoundsV1, BoundsV2, BoundsState, BoundsSmall;
-    // update(): the scratch copy of a block of V (n x CAPI_TS_MAX_RHS) and the log of its steps; the step of the last failed downdate (0: none)
-    matrix<ScalarType, DimensionType, rect> UpdV, UpdLog;
+    // The work of solve(), condition(), error_bounds() and update(), apart from factor()'s `work`: each call reserves its whole need at once and takes
+    // its blocks from it (ops_scope).  SaveIntermediates keeps it at its high-water mark, FlushIntermediates releases it at the end of every call.
+    matmult::arena ops;
+    // update(): the step of the last failed downdate (0: none)
     int update_info = 0;
   };
 
@@ -263,15 +264,16 @@ public:
     const int64_t n = args.localDimension, r = B.num_columns_global();
     if (r < 1 || B.num_rows_global() != n || B.num_rows_local() != n || A.num_rows_local() != n || A.num_columns_local() != n || refine < 0)
       throw std::invalid_argument("cholinv::solve: B must be n x r with r >= 1 (matrix(r, n, 1, 1)), A the factored matrix, refine >= 0");
-    const double* Rfullp = full_storage_R(args, "cholinv::solve");
+    applier ap = make_applier(args, "cholinv::solve");
     CRITTER_START(CI::solve);
     capi_handle_t h = capital::handle();
     CAPITAL_CHECK(capi_stream_select(h, 0));
     const int64_t W = CAPI_TS_MAX_RHS;
-    if (args.X.filled() && args.X.num_columns_local() != r) args.X._destroy_();
-    args.X._register_(r, n, 1, 1);
-    const applier ap = make_applier(args, Rfullp);
-    if (refine > 0) { args.SolveRho._register_(W, n, 1, 1); args.SolveD._register_(W, n, 1, 1); }
+    util::resize_columns(args.X, r, n);
+    ops_scope ops(args.ops, ap.work_blocks + (refine > 0 ? 2 : 0), n, 0);
+    take_applier_work(ap, ops);
+    double* const rho = refine > 0 ? ops.block() : nullptr;
+    double* const corr = refine > 0 ? ops.block() : nullptr;
     auto apply = [&](const double* Bi, double* Xo, int64_t rb) { apply_inverse(ap, Bi, Xo, rb); };
     // Ro (or nothing) <- Bi - A Xi, norm2 (or nothing) <- its squared column norms, from A's upper triangle
     auto resid = [&](int64_t rb, const double* Xi, const double* Bi, double* Ro, double* norm2) {
@@ -284,23 +286,16 @@ public:
       const double* Bj = B.data() + j * n;
       apply(Bj, Xj, rb);
       for (int it = 0; it < refine; ++it) {
-        resid(rb, Xj, Bj, args.SolveRho.data(), nullptr);
-        apply(args.SolveRho.data(), args.SolveD.data(), rb);
-        CAPITAL_CHECK(capi_dgeadd(h, 0, n, rb, 1.0, args.SolveD.data(), n, 1.0, Xj, n));
+        resid(rb, Xj, Bj, rho, nullptr);
+        apply(rho, corr, rb);
+        CAPITAL_CHECK(capi_dgeadd(h, 0, n, rb, 1.0, corr, n, 1.0, Xj, n));
       }
     }
     args.solve_residual_norms.clear();
-    if (residual) {
-      if (args.SolveNorm2.filled() && args.SolveNorm2.num_columns_local() != r) args.SolveNorm2._destroy_();
-      args.SolveNorm2._register_(r, 1, 1, 1);
-      for (int64_t j = 0; j < r; j += W) resid(std::min(W, r - j), args.X.data() + j * n, B.data() + j * n, nullptr, args.SolveNorm2.data() + j);
-      args.solve_residual_norms = args.SolveNorm2.to_host();
-      for (double& v : args.solve_residual_norms) v = std::sqrt(v);
-    }
-    if (!IP::keep_arena) {
-      capital::sync();
-      args.SolveW1._destroy_(); args.SolveW2._destroy_(); args.SolveRho._destroy_(); args.SolveD._destroy_();
-    }
+    if (residual)
+      args.solve_residual_norms = util::residual_norms(args.SolveNorm2, r, nullptr, [&](int64_t j, int64_t rb, double* norm2) {
+        resid(rb, args.X.data() + j * n, B.data() + j * n, nullptr, norm2);
+      });
     CRITTER_STOP(CI::solve);
   }
 
@@ -310,7 +305,7 @@ public:
   //                 its four forms the flags select: args.lacn_applies products with A^-1 on one column, at most 11; each costs what solve() pays for
   //                 one unrefined right-hand side.  0 when the estimate is Inf or NaN (or anorm1 is 0); 1 for n == 0.
   // The estimate is a lower bound of ||A^-1||_1 that is almost always within a factor 3 of it, so rcond errs on the large side.  Nothing of
-  // args.X is touched.  Memory: the estimator's two n x CAPI_TS_MAX_RHS blocks and its state, beside solve()'s own work blocks.
+  // args.X is touched.  Memory, of args.ops: the estimator's two n x CAPI_TS_MAX_RHS blocks and its state, beside the blocks of solve()'s operator.
   template <typename MatrixType, typename ArgType, typename CommType>
   static void condition(const MatrixType& A, ArgType& args, CommType&& CommInfo) {
     static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::condition takes a rect-structured A");
@@ -318,27 +313,27 @@ public:
     require_bounds_abi();
     const int64_t n = args.localDimension;
     if (A.num_rows_local() != n || A.num_columns_local() != n) throw std::invalid_argument("cholinv::condition: A must be the factored matrix");
-    const double* Rfullp = full_storage_R(args, "cholinv::condition");
+    applier ap = make_applier(args, "cholinv::condition");
     args.anorm1 = 0.0; args.rcond = 1.0; args.lacn_applies = 0;
     if (n == 0) return;
     CRITTER_START(CI::condition);
     capi_handle_t h = capital::handle();
     CAPITAL_CHECK(capi_stream_select(h, 0));
-    const applier ap = make_applier(args, Rfullp);
-    register_bounds_work(args, false);
-    double* small = args.BoundsSmall.data();
+    ops_scope ops(args.ops, ap.work_blocks + 2, n, estimator::tail(n));
+    take_applier_work(ap, ops);
+    const estimator es(ops, n);
+    double* const small = es.small;
     {
       const std::vector<double> ones((size_t)n, 1.0);
-      CAPITAL_CHECK(capi_memcpy_h2d(h, args.BoundsV1.data(), ones.data(), sizeof(double) * (size_t)n));
+      CAPITAL_CHECK(capi_memcpy_h2d(h, es.v1, ones.data(), sizeof(double) * (size_t)n));
     }
-    CAPITAL_CHECK(capi_dsym_abs(h, n, 1, A.data(), n, args.BoundsV1.data(), n, nullptr, 0, nullptr, 0, small));
-    args.lacn_applies = estimate(args, ap, 1, nullptr, small + 1);
+    CAPITAL_CHECK(capi_dsym_abs(h, n, 1, A.data(), n, es.v1, n, nullptr, 0, nullptr, 0, small));
+    args.lacn_applies = estimate(es, ap, 1, nullptr, small + 1);
     double out[2];
     CAPITAL_CHECK(capi_memcpy_d2h(h, out, small, sizeof(out)));
     args.anorm1 = out[0];
     const double prod = out[0] * out[1];
     args.rcond = (std::isfinite(out[1]) && std::isfinite(prod) && prod > 0.0) ? 1.0 / prod : 0.0;
-    release_bounds_work(args);
     CRITTER_STOP(CI::condition);
   }
 
@@ -360,7 +355,7 @@ public:
       throw std::invalid_argument("cholinv::error_bounds: B must be n x r with r >= 1 (matrix(r, n, 1, 1)), A the factored matrix");
     if (!args.X.filled() || args.X.num_columns_local() != r || args.X.num_rows_local() != n)
       throw std::invalid_argument("cholinv::error_bounds: the resident X is not that of a solve with this B (no solve yet, or another number of columns)");
-    const double* Rfullp = full_storage_R(args, "cholinv::error_bounds");
+    applier ap = make_applier(args, "cholinv::error_bounds");
     args.solve_ferr.assign((size_t)r, 0.0);
     args.solve_berr.assign((size_t)r, 0.0);
     args.lacn_applies = 0;
@@ -369,9 +364,11 @@ public:
     capi_handle_t h = capital::handle();
     CAPITAL_CHECK(capi_stream_select(h, 0));
     const int64_t W = CAPI_TS_MAX_RHS;
-    const applier ap = make_applier(args, Rfullp);
-    register_bounds_work(args, true);
-    double *small = args.BoundsSmall.data(), *rho = args.BoundsRho.data(), *wt = args.BoundsWt.data();
+    ops_scope ops(args.ops, ap.work_blocks + 4, n, estimator::tail(n));
+    take_applier_work(ap, ops);
+    double *const rho = ops.block(), *const wt = ops.block();
+    const estimator es(ops, n);
+    double* const small = es.small;
     for (int64_t j = 0; j < r; j += W) {
       const int64_t rb = std::min(W, r - j);
       const double* Xj = args.X.data() + j * n;
@@ -380,7 +377,7 @@ public:
       CAPITAL_CHECK(capi_dsym_abs(h, n, rb, A.data(), n, Xj, n, Bj, n, wt, n, nullptr));
       CAPITAL_CHECK(capi_dberr(h, n, rb, rho, n, wt, n, small));                               // berr; wt becomes the forward bound's weights
       CAPITAL_CHECK(capi_dcolamax(h, n, rb, Xj, n, small + 2 * W));                            // ||x_j||_inf
-      args.lacn_applies = std::max(args.lacn_applies, estimate(args, ap, rb, wt, small + W));
+      args.lacn_applies = std::max(args.lacn_applies, estimate(es, ap, rb, wt, small + W));
       double out[3 * CAPI_TS_MAX_RHS];
       CAPITAL_CHECK(capi_memcpy_d2h(h, out, small, sizeof(out)));
       for (int64_t k = 0; k < rb; ++k) {
@@ -389,7 +386,6 @@ public:
         args.solve_ferr[(size_t)(j + k)] = xmax > 0.0 ? est / xmax : est;                      // (dporfs: divided where the norm is positive)
       }
     }
-    release_bounds_work(args);
     CRITTER_STOP(CI::error_bounds);
   }
 
@@ -416,46 +412,41 @@ public:
     args.update_info = 0;
     if (n == 0) return;
     CRITTER_START(CI::update);
-    constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
     capi_handle_t h = capital::handle();
     CAPITAL_CHECK(capi_stream_select(h, 0));
     const int64_t W = CAPI_TS_MAX_RHS, h1 = args.top_split;
     const bool inverse = !args.solve_with_trsm;
     const bool blocks = inverse && !args.complete_inv && h1 > 0 && h1 < n;
-    // the image that takes the steps: the full-storage working image where one is resident (never one that FlushIntermediates released), else the
-    // packed triangle in place; NoSerialize: the rect structure itself
-    const bool viaR = packed && IP::keep_arena && args.Rfull.filled(), viaI = packed && inverse && IP::keep_arena && args.Rinvfull.filled();
-    double* const Rp = viaR ? args.Rfull.data() : (double*)args.R.data();
-    double* const Ip = !inverse ? nullptr : (viaI ? args.Rinvfull.data() : (double*)args.Rinv.data());
-    const int64_t ldR = (viaR || !packed) ? n : 0, ldI = (viaI || !packed) ? n : 0;
-    args.UpdV._register_(W, n, 1, 1);
-    args.UpdLog._register_((int64_t)((capi_dchud_log_bytes(n, W) + 7) / 8), 1, 1, 1);
+    // the images that take the steps
+    const image Rw = pick_image(args.R, args.Rfull, n, image_use::in_place, "cholinv::update");
+    const image Iw = inverse ? pick_image(args.Rinv, args.Rinvfull, n, image_use::in_place, "cholinv::update") : image();
+    const typename image::block Rb = Rw.at(0, 0), Ib = Iw.at(0, 0);
+    const int64_t log_count = (int64_t)((capi_dchud_log_bytes(n, W) + 7) / 8);
+    ops_scope ops(args.ops, 1, n, even(log_count));
+    double *const v = ops.block(), *const log = ops.piece(log_count);
     int info = 0;
     int64_t bad_block = 0;
     for (int64_t j = 0; j < r && info == 0; j += W) {
       const int64_t rb = std::min(W, r - j);
-      CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, V.data() + j * n, n, args.UpdV.data(), n));
-      CAPITAL_CHECK(capi_dchud(h, sign, n, rb, Rp, ldR, 0, args.UpdV.data(), n, args.UpdLog.data(), &info));
+      CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, V.data() + j * n, n, v, n));
+      CAPITAL_CHECK(capi_dchud(h, sign, n, rb, Rb.p, Rb.ldt, Rb.col0, v, n, log, &info));
       if (info != 0) { bad_block = j; break; }
       if (!inverse) continue;
       if (blocks) {
-        CAPITAL_CHECK(capi_dchud_inv(h, sign, n, rb, Ip, ldI, 0, args.UpdLog.data(), 0, h1));
-        CAPITAL_CHECK(capi_dchud_inv(h, sign, n, rb, Ip, ldI, 0, args.UpdLog.data(), h1, n));
+        CAPITAL_CHECK(capi_dchud_inv(h, sign, n, rb, Ib.p, Ib.ldt, Ib.col0, log, 0, h1));
+        CAPITAL_CHECK(capi_dchud_inv(h, sign, n, rb, Ib.p, Ib.ldt, Ib.col0, log, h1, n));
       } else {
-        CAPITAL_CHECK(capi_dchud_inv(h, sign, n, rb, Ip, ldI, 0, args.UpdLog.data(), 0, n));
+        CAPITAL_CHECK(capi_dchud_inv(h, sign, n, rb, Ib.p, Ib.ldt, Ib.col0, log, 0, n));
       }
     }
     if (info == 0) {
-      if (viaR) serialize<uppertri, uppertri>::invoke(args.Rfull, args.R, 0, n, 0, n, 0, n, 0, n);
-      if (viaI) serialize<uppertri, uppertri>::invoke(args.Rinvfull, args.Rinv, 0, n, 0, n, 0, n, 0, n);
+      // a working image took the steps: the packed factor beside it follows
+      if (Rw.working) serialize<uppertri, uppertri>::invoke(args.Rfull, args.R, 0, n, 0, n, 0, n, 0, n);
+      if (Iw.working) serialize<uppertri, uppertri>::invoke(args.Rinvfull, args.Rinv, 0, n, 0, n, 0, n, 0, n);
       CAPITAL_CHECK(capi_dsyrk(h, CAPI_UPPER, CAPI_NOTRANS, n, r, (double)sign, V.data(), n, 1.0, A.data(), n));
     } else {
       args.factored = false;
       args.update_info = info;
-    }
-    if (!IP::keep_arena) {
-      capital::sync();
-      args.UpdV._destroy_(); args.UpdLog._destroy_();
     }
     CRITTER_STOP(CI::update);
     if (info != 0)
@@ -629,66 +620,105 @@ public:
 
 private:
   // ---- what solve(), condition() and error_bounds() share: the resident factors seen as the operator A^-1 on a thin block ----
+  // One resident image of a factor: column-major with leading dimension ld, or, ld == 0, the packed upper triangle.
+  struct image {
+    double* p = nullptr;
+    int64_t ld = 0;
+    bool working = false;          // the full-storage working image that SaveIntermediates keeps BESIDE the packed factor
+    // the block whose first element is (i0, j0) as the thin entry points take it: a view into the packed triangle has ldt == 0 and its first column
+    struct block { double* p; int64_t ldt, col0; };
+    block at(int64_t i0, int64_t j0) const { return ld > 0 ? block{p + i0 + j0 * ld, ld, 0} : block{p + j0 * (j0 + 1) / 2 + i0, 0, j0}; }
+  };
+  enum class image_use { thin_read, full_storage, in_place };
+  // Which image of a factor an operation touches: `structured` is R or Rinv as factor() returns it, `full` its full-storage working image.
+  //   thin_read      the thin kernels read the factor as it lies, packed or rect
+  //   full_storage   capi_dtrsm takes column-major storage: the working image, or the rect structure; refused where neither exists
+  //   in_place       update() steps the working image where one is resident (and packs it again), else the factor itself, packed or rect
+  // (FlushIntermediates promises that no working image outlives factor(): none is relied on there, whatever is still allocated)
+  template <typename S, typename F>
+  static image pick_image(S& structured, F& full, int64_t n, image_use use, const char* who) {
+    constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
+    if (use != image_use::thin_read && packed && IP::keep_arena && full.filled()) return image{full.data(), n, true};
+    if (use == image_use::full_storage && packed)
+      throw std::logic_error(std::string(who) + ": TRSM mode with Serialize + FlushIntermediates leaves only the packed R, and capi_dtrsm takes full "
+                             "storage: use SaveIntermediates or NoSerialize with solve_with_trsm");
+    return image{(double*)structured.data(), packed ? 0 : n, false};
+  }
+
+  static int64_t even(int64_t count) { return (count + 1) & ~(int64_t)1; }        // what arena::take makes of a count
+  // The work of one operation on the factors, from args.ops: `blocks` blocks of n x CAPI_TS_MAX_RHS doubles and `tail` doubles (a sum of even() counts)
+  // of odd-sized pieces.  The whole need is reserved here, before any pointer is held (reserve may free and allocate anew).  The blocks are taken FIRST:
+  // each is 256 n bytes, so every one lies at a multiple of 256 bytes from the arena's base -- no operand is less aligned than in an allocation of its
+  // own -- and the pieces follow them.  Nothing is zeroed and nothing needs to be: no kernel of these operations reads work that it or a kernel before it
+  // in the same call has not written (beta == 0 products do not read C; capi_dresid_sym, capi_dsym_abs and capi_dlacn_block(init) only store to their
+  // outputs; capi_dchud reads r columns of V and capi_dchud_inv only logged steps; the rows of w2 above h1 are never addressed).  On every exit,
+  // exceptions included, FlushIntermediates drains the stream and releases the arena (a failure of that drain shows at the next checked call);
+  // SaveIntermediates keeps the arena at its high-water mark.
+  struct ops_scope {
+    matmult::arena& a;
+    const int64_t blk;
+    ops_scope(matmult::arena& a, int64_t blocks, int64_t n, int64_t tail) : a(a), blk(n * (int64_t)CAPI_TS_MAX_RHS) { a.reserve(std::max<int64_t>(blocks * blk + tail, 2)); }
+    ops_scope(const ops_scope&) = delete;
+    ops_scope& operator=(const ops_scope&) = delete;
+    ~ops_scope() {
+      if (IP::keep_arena) return;
+      if (capital::ctx().handle) (void)capi_sync(capital::ctx().handle);
+      a.release();
+    }
+    double* block() { return a.take(blk); }
+    double* piece(int64_t count) { return a.take(count); }
+  };
+
+  // ---- what solve(), condition() and error_bounds() share: the resident factors seen as the operator A^-1 on a thin block ----
   struct applier {
     capi_handle_t h;
     int64_t n, h1;
     bool subst, trsm, blocks;
-    const double *Rp, *Ip, *Rfullp;
-    double *w1, *w2;
+    image R, Rinv, Rfull;            // Rfull: TRSM mode without substitution only
+    int work_blocks;                 // n x CAPI_TS_MAX_RHS blocks of the form that the flags select
+    double *w1 = nullptr, *w2 = nullptr;
   };
-  // the full-storage R that capi_dtrsm needs (TRSM mode without substitution), or null where no form of the solve reads one
+  // `who` opens the refusal of a form that has no image to run on
   template <typename ArgType>
-  static const double* full_storage_R(ArgType& args, const char* who) {
-    constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
-    if (!(args.solve_with_trsm && !args.solve_by_substitution)) return nullptr;
-    // (FlushIntermediates promises that no full-storage working image outlives factor(): none is relied on there, whatever is still allocated)
-    const double* Rfullp = packed ? (IP::keep_arena && args.Rfull.filled() ? args.Rfull.data() : nullptr) : (const double*)args.R.data();
-    if (!Rfullp)
-      throw std::logic_error(std::string(who) + ": TRSM mode with Serialize + FlushIntermediates leaves only the packed R, and capi_dtrsm takes full "
-                             "storage: use SaveIntermediates or NoSerialize with solve_with_trsm");
-    return Rfullp;
-  }
-  // registers the work blocks of the form that the flags select
-  template <typename ArgType>
-  static applier make_applier(ArgType& args, const double* Rfullp) {
-    const int64_t W = CAPI_TS_MAX_RHS, n = args.localDimension, h1 = args.top_split;
+  static applier make_applier(ArgType& args, const char* who) {
+    const int64_t n = args.localDimension, h1 = args.top_split;
     applier c;
     c.h = capital::handle();
     c.n = n; c.h1 = h1;
     c.subst = args.solve_by_substitution; c.trsm = args.solve_with_trsm;
     c.blocks = !c.subst && !c.trsm && !args.complete_inv && h1 > 0 && h1 < n;
-    if (!c.subst) args.SolveW1._register_(W, n, 1, 1);
-    if (c.blocks) args.SolveW2._register_(W, n, 1, 1);
-    c.Rp = (const double*)args.R.data();
-    c.Ip = c.trsm ? nullptr : (const double*)args.Rinv.data();
-    c.Rfullp = Rfullp;
-    c.w1 = c.subst ? nullptr : args.SolveW1.data();
-    c.w2 = c.blocks ? args.SolveW2.data() : nullptr;
+    c.R = pick_image(args.R, args.Rfull, n, image_use::thin_read, who);
+    if (!c.trsm) c.Rinv = pick_image(args.Rinv, args.Rinvfull, n, image_use::thin_read, who);
+    if (c.trsm && !c.subst) c.Rfull = pick_image(args.R, args.Rfull, n, image_use::full_storage, who);
+    c.work_blocks = (c.subst || c.trsm) ? 0 : (c.blocks ? 2 : 1);
     return c;
+  }
+  static void take_applier_work(applier& c, ops_scope& ops) {
+    if (c.work_blocks > 0) c.w1 = ops.block();
+    if (c.work_blocks > 1) c.w2 = ops.block();
   }
   // Xo (n x rb, ld n) <- A^-1 Bi; Bi is not written and Xo != Bi
   static void apply_inverse(const applier& c, const double* Bi, double* Xo, int64_t rb) {
-    constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
     capi_handle_t h = c.h;
     const int64_t n = c.n, h1 = c.h1;
-    const double *Rp = c.Rp, *Ip = c.Ip;
-    // the block of a factor whose first element is (i0, j0): a view into the packed triangle (ldt == 0, col0 = j0) or into the rect structure
-    auto thin = [&](const double* F, int shape, int trans, int64_t i0, int64_t j0, int64_t m, int64_t k, int64_t rb, double alpha, const double* Bp,
+    const image &Rp = c.R, &Ip = c.Rinv;
+    auto thin = [&](const image& F, int shape, int trans, int64_t i0, int64_t j0, int64_t m, int64_t k, int64_t rb, double alpha, const double* Bp,
                     double beta, double* Cp) {
-      const double* Tp = packed ? F + j0 * (j0 + 1) / 2 + i0 : F + i0 + j0 * n;
-      CAPITAL_CHECK(capi_dtrmm_thin(h, shape, trans, m, k, rb, alpha, Tp, packed ? 0 : n, packed ? j0 : 0, Bp, n, beta, Cp, n));
+      const typename image::block T = F.at(i0, j0);
+      CAPITAL_CHECK(capi_dtrmm_thin(h, shape, trans, m, k, rb, alpha, T.p, T.ldt, T.col0, Bp, n, beta, Cp, n));
     };
     if (c.subst) {
+      const typename image::block T = Rp.at(0, 0);
       CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));
-      CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_TRANS, n, rb, Rp, packed ? 0 : n, 0, Xo, n));             // y = R^-T b
-      CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_NOTRANS, n, rb, Rp, packed ? 0 : n, 0, Xo, n));           // x = R^-1 y
+      CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_TRANS, n, rb, T.p, T.ldt, T.col0, Xo, n));                // y = R^-T b
+      CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_NOTRANS, n, rb, T.p, T.ldt, T.col0, Xo, n));              // x = R^-1 y
       return;
     }
     double* w1 = c.w1;
     if (c.trsm) {
       CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));
-      CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_TRANS, CAPI_NONUNIT, n, rb, 1.0, c.Rfullp, n, Xo, n));
-      CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, n, rb, 1.0, c.Rfullp, n, Xo, n));
+      CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_TRANS, CAPI_NONUNIT, n, rb, 1.0, c.Rfull.p, c.Rfull.ld, Xo, n));
+      CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, n, rb, 1.0, c.Rfull.p, c.Rfull.ld, Xo, n));
     } else if (!c.blocks) {
       thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, 0, 0, n, n, rb, 1.0, Bi, 0.0, w1);
       thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, 0, 0, n, n, rb, 1.0, w1, 0.0, Xo);
@@ -719,37 +749,26 @@ private:
     if (!&capi_dsym_abs || !&capi_dberr || !&capi_dcolamax || !&capi_dlacn_block || !&capi_dlacn_state_bytes || !&capi_dresid_sym)
       throw std::logic_error("cholinv: this C-ABI library has no capi_dsym_abs / capi_dberr / capi_dcolamax / capi_dlacn_block: no condition estimate, no error bounds");
   }
+  // the work of the estimator: its two n x CAPI_TS_MAX_RHS blocks, then its state and the 4 CAPI_TS_MAX_RHS small results of condition() / error_bounds()
+  struct estimator {
+    double *v1, *v2, *state, *small;
+    static int64_t state_count(int64_t n) { return (int64_t)((capi_dlacn_state_bytes(n, CAPI_TS_MAX_RHS) + 7) / 8); }
+    static int64_t tail(int64_t n) { return even(state_count(n)) + 4 * (int64_t)CAPI_TS_MAX_RHS; }
+    estimator(ops_scope& ops, int64_t n) : v1(ops.block()), v2(ops.block()), state(ops.piece(state_count(n))), small(ops.piece(4 * (int64_t)CAPI_TS_MAX_RHS)) {}
+  };
   // the estimator's loop over the shared operator: est (device, rb doubles) <- the estimates for the weight columns Wt (or none).  Returns the products
-  template <typename ArgType>
-  static int estimate(ArgType& args, const applier& ap, int64_t rb, const double* Wt, double* est) {
+  static int estimate(const estimator& es, const applier& ap, int64_t rb, const double* Wt, double* est) {
     const int64_t n = ap.n;
-    double *v = args.BoundsV1.data(), *y = args.BoundsV2.data();
+    double *v = es.v1, *y = es.v2;
     int active = 0, applies = 0;
-    CAPITAL_CHECK(capi_dlacn_block(ap.h, 1, n, rb, v, n, Wt, n, args.BoundsState.data(), est, &active));
+    CAPITAL_CHECK(capi_dlacn_block(ap.h, 1, n, rb, v, n, Wt, n, es.state, est, &active));
     while (active > 0) {
       apply_inverse(ap, v, y, rb);
       ++applies;
       std::swap(v, y);
-      CAPITAL_CHECK(capi_dlacn_block(ap.h, 0, n, rb, v, n, Wt, n, args.BoundsState.data(), est, &active));
+      CAPITAL_CHECK(capi_dlacn_block(ap.h, 0, n, rb, v, n, Wt, n, es.state, est, &active));
     }
     return applies;
-  }
-  template <typename ArgType>
-  static void register_bounds_work(ArgType& args, bool weights) {
-    const int64_t W = CAPI_TS_MAX_RHS, n = args.localDimension;
-    args.BoundsV1._register_(W, n, 1, 1);
-    args.BoundsV2._register_(W, n, 1, 1);
-    args.BoundsState._register_((int64_t)((capi_dlacn_state_bytes(n, W) + 7) / 8), 1, 1, 1);
-    args.BoundsSmall._register_(4 * W, 1, 1, 1);
-    if (weights) { args.BoundsRho._register_(W, n, 1, 1); args.BoundsWt._register_(W, n, 1, 1); }
-  }
-  template <typename ArgType>
-  static void release_bounds_work(ArgType& args) {
-    if (IP::keep_arena) return;
-    capital::sync();
-    args.SolveW1._destroy_(); args.SolveW2._destroy_();
-    args.BoundsRho._destroy_(); args.BoundsWt._destroy_(); args.BoundsV1._destroy_(); args.BoundsV2._destroy_(); args.BoundsState._destroy_();
-    args.BoundsSmall._destroy_();
   }
 
   // event slots of the top-level overlap (matmult::summa's pipe uses slots below 1000)

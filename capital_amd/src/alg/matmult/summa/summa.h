@@ -41,7 +41,7 @@ struct arena {
   void reserve(int64_t count) {
     if (count > cap) {
       capital::sync();
-      capital::dev_free(base);
+      release();                                // (an allocation that throws must not leave the freed block behind)
       base = capital::dev_alloc(count);
       cap = count;
     }

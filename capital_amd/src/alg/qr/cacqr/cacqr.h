@@ -186,18 +186,7 @@ public:
     CAPITAL_CHECK(capi_reset_info(h));
     args.potrf_info = 0;
     args.sweep_shift.clear(); args.sweep_trace.clear(); args.sweep_cond_bound.clear();
-    CRITTER_START(CQR::gram);
-    CAPITAL_CHECK(capi_dsyrk(h, CAPI_UPPER, CAPI_TRANS, n, m_loc, 1.0, A.data(), m_loc, 0.0, args.G.data(), n));       // K7
-    if (CommInfo.size > 1) {                                                                                       // C8
-      if (SP::packed_gram) {
-        serialize<uppertri, uppertri>::invoke(args.G, args.Gpacked, 0, n, 0, n, 0, n, 0, n);
-        CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, args.Gpacked.data(), args.Gpacked.num_elems()));
-        serialize<uppertri, uppertri>::invoke(args.Gpacked, args.G, 0, n, 0, n, 0, n, 0, n);
-      } else {
-        CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, args.G.data(), n * n));
-      }
-    }
-    CRITTER_STOP(CQR::gram);
+    gram_1d(A.data(), false, m_loc, n, args.G, args.Gpacked, CommInfo);
     CRITTER_START(CQR::formR);
     // the factor of a shifted sweep's shift, or the user's tolerance squared (G holds squared norms)
     const double floor_tol = 11.0 * ((double)m_glob * (double)n + (double)n * (double)(n + 1)) * 0x1p-53;
@@ -220,19 +209,11 @@ public:
     CAPITAL_CHECK(capi_dgemm(h, CAPI_NOTRANS, CAPI_NOTRANS, m_loc, k, n, 1.0, A.data(), m_loc, args.R1.data(), n, 0.0, args.Q.data(), m_loc));
     CRITTER_STOP(CQR::formR);
     {
-      // one plain sweep on the m_loc x k panel: sweep_1d works on args.G / Ginv / Gpacked as blocks of the panel's own order, so k x k blocks stand in
-      // for them while it runs; [R11 R12] stays where capi_dpstrf left it
+      // one plain sweep on the m_loc x k panel, on blocks of the panel's own order; [R11 R12] stays where capi_dpstrf left it
       matrix<double, Dim, rect> Gk(k, k, 1, 1), Gik(k, k, 1, 1);
       matrix<double, Dim, uppertri> Gpk;
       if (SP::packed_gram) Gpk._register_(k, k, 1, 1);
-      std::swap(args.G, Gk); std::swap(args.Ginv, Gik); std::swap(args.Gpacked, Gpk);
-      try {
-        sweep_1d(args.Q.data(), args.Q.scratch(), m_loc, k, args, CommInfo);
-      } catch (...) {
-        std::swap(args.G, Gk); std::swap(args.Ginv, Gik); std::swap(args.Gpacked, Gpk);
-        throw;
-      }
-      std::swap(args.G, Gk); std::swap(args.Ginv, Gik); std::swap(args.Gpacked, Gpk);
+      sweep_1d(args.Q.data(), args.Q.scratch(), m_loc, k, Gk, Gik, Gpk, args, CommInfo);
       args.Q.swap();
       // Rp(0:k, :) = R2 [R11 R12]: the leading block's strictly lower part was never written
       CAPITAL_CHECK(capi_dtrizero(h, CAPI_UPPER, k, args.G.data(), n));
@@ -256,44 +237,44 @@ public:
     if (CommInfo.c != 1) throw std::logic_error("qr::cacqr::least_squares is built for the 1-D variant (c == 1) only");
     if (!&capi_dgemtn_ts || !&capi_dresid_ts)
       throw std::logic_error("qr::cacqr: this C-ABI library has no capi_dgemtn_ts / capi_dresid_ts: no least-squares solve");
-    if (args.pivoted) { least_squares_pivoted(A, B, args, CommInfo, residual); return; }
-    if (!args.factored || args.potrf_info != 0 || !args.Q.filled() || !args.R.filled())
-      throw std::logic_error("qr::cacqr::least_squares: factor() has not run or did not succeed: there is no valid Q and R to solve with");
+    // On factor_pivoted's factors the basic solution X = P [R11^-1 (Q^T B); 0]: Q has k = rank columns, R11 is Rp's leading block
+    const bool piv = args.pivoted;
+    if (piv && !&capi_drow_scatter) throw std::logic_error("qr::cacqr: this C-ABI library has no capi_drow_scatter: no solve on pivoted factors");
+    if (!args.factored || args.potrf_info != 0 || !args.Q.filled() || (piv ? !args.Rp.filled() || !args.Piv.filled() || args.rank < 1 : !args.R.filled()))
+      throw std::logic_error(piv ? "qr::cacqr::least_squares: factor_pivoted() did not succeed: there is no valid Q and R to solve with"
+                                 : "qr::cacqr::least_squares: factor() has not run or did not succeed: there is no valid Q and R to solve with");
     capi_handle_t h = capital::handle();
-    const int64_t n = A.num_columns_global(), m_loc = A.num_rows_local(), r = B.num_columns_global();
+    const int64_t n = A.num_columns_global(), m_loc = A.num_rows_local(), r = B.num_columns_global(), k = piv ? args.rank : n;
     if (r < 1 || B.num_rows_local() != m_loc || B.num_rows_global() != A.num_rows_global() || args.Q.num_rows_local() != m_loc ||
-        args.Q.num_columns_global() != n)
+        args.Q.num_columns_global() != n || k > n)
       throw std::invalid_argument("qr::cacqr::least_squares: B must have r >= 1 columns and A's rows, distributed as A, and A must be the factored matrix");
     CRITTER_START(CQR::lstsq);
-    if (args.X.filled() && args.X.num_columns_local() != r) args.X._destroy_();
-    args.X._register_(r, n, 1, 1);
+    util::resize_columns(args.X, r, n);
     const int64_t W = CAPI_TS_MAX_RHS;
-    // C = Q^T B (the last sweep leaves Q column-major).  capi_dgemtn_ts as it stands is UNMEASURED.  An earlier form of it lost to
-    // capi_dgemm(T, N) on the 128-tile kernel on both shapes that were timed, 2^22 x 256 (3.7-3.9 against 2.5-2.8 ms) and 2^21 x 1024
-    // (DESIGN.md section 4); on that evidence tall panels of width >= 256 take that product.  Narrower or shorter panels take the
-    // streaming kernel; no form of it was timed there.
-    const bool by_gemm = n >= 256 && m_loc >= 64 * n;
+    // C = Q^T B (k x r, leading dimension n; the last sweep leaves Q column-major), in X itself or, pivoted, in X's second buffer, whose rows >= k stay
+    // zero.  capi_dgemtn_ts as it stands is UNMEASURED.  An earlier form of it lost to capi_dgemm(T, N) on the 128-tile kernel on both shapes that
+    // were timed, 2^22 x 256 (3.7-3.9 against 2.5-2.8 ms) and 2^21 x 1024; on that evidence tall panels of width >= 256 take
+    // that product.  Narrower or shorter panels take the streaming kernel; no form of it was timed there.
+    double* const C = piv ? args.X.scratch() : args.X.data();
+    const bool by_gemm = k >= 256 && m_loc >= 64 * k;
     for (int64_t j = 0; j < r; j += W) {
       const int64_t rb = std::min(W, r - j);
-      if (by_gemm) CAPITAL_CHECK(capi_dgemm(h, CAPI_TRANS, CAPI_NOTRANS, n, rb, m_loc, 1.0, args.Q.data(), m_loc, B.data() + j * m_loc, m_loc, 0.0, args.X.data() + j * n, n));
-      else CAPITAL_CHECK(capi_dgemtn_ts(h, m_loc, n, rb, 1.0, args.Q.data(), m_loc, B.data() + j * m_loc, m_loc, 0.0, args.X.data() + j * n, n));
+      if (by_gemm) CAPITAL_CHECK(capi_dgemm(h, CAPI_TRANS, CAPI_NOTRANS, k, rb, m_loc, 1.0, args.Q.data(), m_loc, B.data() + j * m_loc, m_loc, 0.0, C + j * n, n));
+      else CAPITAL_CHECK(capi_dgemtn_ts(h, m_loc, k, rb, 1.0, args.Q.data(), m_loc, B.data() + j * m_loc, m_loc, 0.0, C + j * n, n));
     }
-    if (CommInfo.size > 1) CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, args.X.data(), n * r));
-    args.G._register_(n, n, 1, 1);                                                                                  // full-storage image of R
-    serialize<uppertri, uppertri>::invoke(args.R, args.G, 0, n, 0, n, 0, n, 0, n);
-    CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, n, r, 1.0, args.G.data(), n, args.X.data(), n));   // X = R^-1 C
+    if (CommInfo.size > 1) CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, C, n * r));
+    if (piv) {
+      CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, k, r, 1.0, args.Rp.data(), n, C, n));          // Y = R11^-1 C
+      CAPITAL_CHECK(capi_drow_scatter(h, 0, k, r, n, C, n, reinterpret_cast<const int*>(args.Piv.data()), args.X.data(), n));
+    } else {
+      CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, n, r, 1.0, full_storage_R(args, n), n, C, n));  // X = R^-1 C
+    }
     args.ls_residual_norms.clear();
-    if (residual) {
-      if (args.LsNorm2.filled() && args.LsNorm2.num_columns_local() != r) args.LsNorm2._destroy_();
-      args.LsNorm2._register_(r, 1, 1, 1);
-      for (int64_t j = 0; j < r; j += W)
-        CAPITAL_CHECK(capi_dresid_ts(h, m_loc, n, std::min(W, r - j), A.data(), m_loc, args.X.data() + j * n, n, B.data() + j * m_loc, m_loc, nullptr, 0,
-                                     args.LsNorm2.data() + j));
-      if (CommInfo.size > 1) CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, args.LsNorm2.data(), r));
-      args.ls_residual_norms = args.LsNorm2.to_host();
-      for (double& v : args.ls_residual_norms) v = std::sqrt(v);
-    }
-    if (!IP::keep_work) { capital::sync(); args.G._destroy_(); }
+    if (residual)
+      args.ls_residual_norms = util::residual_norms(args.LsNorm2, r, CommInfo.size > 1 ? CommInfo.world : nullptr, [&](int64_t j, int64_t rb, double* norm2) {
+        CAPITAL_CHECK(capi_dresid_ts(h, m_loc, n, rb, A.data(), m_loc, args.X.data() + j * n, n, B.data() + j * m_loc, m_loc, nullptr, 0, norm2));
+      });
+    if (!piv && !IP::keep_work) { capital::sync(); args.G._destroy_(); }
     CRITTER_STOP(CQR::lstsq);
   }
 
@@ -309,13 +290,12 @@ public:
     capi_handle_t h = capital::handle();
     const int64_t n = args.Q.num_columns_global(), m_loc = args.Q.num_rows_local();
     CRITTER_START(CQR::svd);
-    args.G._register_(n, n, 1, 1);                                                                                  // full-storage image of R
-    serialize<uppertri, uppertri>::invoke(args.R, args.G, 0, n, 0, n, 0, n, 0, n);
+    double* const Rfull = full_storage_R(args, n);
     args.Sigma._register_(1, n, 1, 1);
     args.V._register_(n, n, 1, 1);
     if (left) args.UR._register_(n, n, 1, 1);
     int sweeps = 0;
-    CAPITAL_CHECK(capi_dgesvj(h, n, args.G.data(), n, left ? args.UR.data() : nullptr, n, args.Sigma.data(), args.V.data(), n, &sweeps));
+    CAPITAL_CHECK(capi_dgesvj(h, n, Rfull, n, left ? args.UR.data() : nullptr, n, args.Sigma.data(), args.V.data(), n, &sweeps));
     args.svd_sweeps = sweeps;
     if (left) {
       args.U._register_(n, args.Q.num_rows_global(), CommInfo.c, CommInfo.d);
@@ -345,74 +325,51 @@ public:
   }
 
 protected:
-  // least_squares on factor_pivoted's factors: the basic solution X = P [R11^-1 (Q^T B); 0] -- C = Q^T B (k x r, the kernel choice of the plain
-  // path at width k) and its all-reduce, Y = R11^-1 C by capi_dtrsm on Rp's leading block, X by capi_drow_scatter, residual norms on A as there
-  template <typename MatrixType, typename ArgType, typename CommType>
-  static void least_squares_pivoted(const MatrixType& A, const MatrixType& B, ArgType& args, CommType&& CommInfo, bool residual) {
-    if (!&capi_drow_scatter) throw std::logic_error("qr::cacqr: this C-ABI library has no capi_drow_scatter: no solve on pivoted factors");
-    if (!args.factored || args.potrf_info != 0 || !args.Q.filled() || !args.Rp.filled() || !args.Piv.filled() || args.rank < 1)
-      throw std::logic_error("qr::cacqr::least_squares: factor_pivoted() did not succeed: there is no valid Q and R to solve with");
-    capi_handle_t h = capital::handle();
-    const int64_t n = A.num_columns_global(), m_loc = A.num_rows_local(), r = B.num_columns_global(), k = args.rank;
-    if (r < 1 || B.num_rows_local() != m_loc || B.num_rows_global() != A.num_rows_global() || args.Q.num_rows_local() != m_loc ||
-        args.Q.num_columns_global() != n || k > n)
-      throw std::invalid_argument("qr::cacqr::least_squares: B must have r >= 1 columns and A's rows, distributed as A, and A must be the factored matrix");
-    CRITTER_START(CQR::lstsq);
-    if (args.X.filled() && args.X.num_columns_local() != r) args.X._destroy_();
-    args.X._register_(r, n, 1, 1);
-    double* const Y = args.X.scratch();                                                                             // n x r; rows >= k stay zero
-    const int64_t W = CAPI_TS_MAX_RHS;
-    const bool by_gemm = k >= 256 && m_loc >= 64 * k;
-    for (int64_t j = 0; j < r; j += W) {
-      const int64_t rb = std::min(W, r - j);
-      if (by_gemm) CAPITAL_CHECK(capi_dgemm(h, CAPI_TRANS, CAPI_NOTRANS, k, rb, m_loc, 1.0, args.Q.data(), m_loc, B.data() + j * m_loc, m_loc, 0.0, Y + j * n, n));
-      else CAPITAL_CHECK(capi_dgemtn_ts(h, m_loc, k, rb, 1.0, args.Q.data(), m_loc, B.data() + j * m_loc, m_loc, 0.0, Y + j * n, n));
-    }
-    if (CommInfo.size > 1) CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, Y, n * r));
-    CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, k, r, 1.0, args.Rp.data(), n, Y, n));  // Y = R11^-1 C
-    CAPITAL_CHECK(capi_drow_scatter(h, 0, k, r, n, Y, n, reinterpret_cast<const int*>(args.Piv.data()), args.X.data(), n));
-    args.ls_residual_norms.clear();
-    if (residual) {
-      if (args.LsNorm2.filled() && args.LsNorm2.num_columns_local() != r) args.LsNorm2._destroy_();
-      args.LsNorm2._register_(r, 1, 1, 1);
-      for (int64_t j = 0; j < r; j += W)
-        CAPITAL_CHECK(capi_dresid_ts(h, m_loc, n, std::min(W, r - j), A.data(), m_loc, args.X.data() + j * n, n, B.data() + j * m_loc, m_loc, nullptr, 0,
-                                     args.LsNorm2.data() + j));
-      if (CommInfo.size > 1) CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, args.LsNorm2.data(), r));
-      args.ls_residual_norms = args.LsNorm2.to_host();
-      for (double& v : args.ls_residual_norms) v = std::sqrt(v);
-    }
-    CRITTER_STOP(CQR::lstsq);
+  // the full-storage image of R that capi_dtrsm and capi_dgesvj take, in the Gram work block (registered anew when the policy released it)
+  template <typename ArgType>
+  static double* full_storage_R(ArgType& args, int64_t n) {
+    args.G._register_(n, n, 1, 1);
+    serialize<uppertri, uppertri>::invoke(args.R, args.G, 0, n, 0, n, 0, n, 0, n);
+    return args.G.data();
   }
 
-  // one CholeskyQR sweep: dst <- src * chol(src^T src)^-1 ; leaves R in args.G and R^-1 in args.Ginv
-  // src_tiled / dst_tiled: the panel is a "panel32" image (include/capital_hip.h) instead of column-major -- the intermediate panels Q1, Q2, ..
-  // rec != nullptr (runs with num_shifted > 0): the sweep's 4-double device record; shifted: equilibrate and shift the Gram matrix (m_glob rows)
-  template <typename ArgType, typename CommType>
-  static void sweep_1d(const double* src, double* dst, int64_t m_loc, int64_t n, ArgType& args, CommType&& CommInfo, bool src_tiled = false,
-                       bool dst_tiled = false, bool shifted = false, double* rec = nullptr, int64_t m_glob = 0) {
+  // K7 + C8: G <- src^T src (n x n, its upper triangle), summed over the ranks -- with Serialize as the n (n + 1) / 2 doubles of Gpacked.
+  // src_tiled: the panel is a "panel32" image (include/capital_hip.h) instead of column-major
+  template <typename GramType, typename PackedType, typename CommType>
+  static void gram_1d(const double* src, bool src_tiled, int64_t m_loc, int64_t n, GramType& G, PackedType& Gpacked, CommType&& CommInfo) {
     capi_handle_t h = capital::handle();
     CRITTER_START(CQR::gram);
-    if (src_tiled) CAPITAL_CHECK(capi_dsyrk_panel32(h, n, m_loc, 1.0, src, 0.0, args.G.data(), n));                  // K7 on the image
-    else CAPITAL_CHECK(capi_dsyrk(h, CAPI_UPPER, CAPI_TRANS, n, m_loc, 1.0, src, m_loc, 0.0, args.G.data(), n));      // K7
+    if (src_tiled) CAPITAL_CHECK(capi_dsyrk_panel32(h, n, m_loc, 1.0, src, 0.0, G.data(), n));                       // K7 on the image
+    else CAPITAL_CHECK(capi_dsyrk(h, CAPI_UPPER, CAPI_TRANS, n, m_loc, 1.0, src, m_loc, 0.0, G.data(), n));           // K7
     if (CommInfo.size > 1) {                                                                                       // C8
       if (SP::packed_gram) {
-        serialize<uppertri, uppertri>::invoke(args.G, args.Gpacked, 0, n, 0, n, 0, n, 0, n);
-        CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, args.Gpacked.data(), args.Gpacked.num_elems()));
-        serialize<uppertri, uppertri>::invoke(args.Gpacked, args.G, 0, n, 0, n, 0, n, 0, n);
+        serialize<uppertri, uppertri>::invoke(G, Gpacked, 0, n, 0, n, 0, n, 0, n);
+        CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, Gpacked.data(), Gpacked.num_elems()));
+        serialize<uppertri, uppertri>::invoke(Gpacked, G, 0, n, 0, n, 0, n, 0, n);
       } else {
-        CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, args.G.data(), n * n));
+        CAPITAL_CHECK(capi_allreduce_sum(CommInfo.world, G.data(), n * n));
       }
     }
     CRITTER_STOP(CQR::gram);
+  }
+
+  // one CholeskyQR sweep: dst <- src * chol(src^T src)^-1 on the blocks it is given, all of order n: leaves R in G and R^-1 in Ginv; Gpacked is the
+  // all-reduce's transfer image (Serialize).  src_tiled / dst_tiled: the panel is a "panel32" image instead of column-major -- the intermediate
+  // panels Q1, Q2, ..  rec != nullptr (runs with num_shifted > 0): the sweep's 4-double device record; shifted: equilibrate and shift the Gram
+  // matrix (m_glob rows)
+  template <typename GramType, typename PackedType, typename ArgType, typename CommType>
+  static void sweep_1d(const double* src, double* dst, int64_t m_loc, int64_t n, GramType& G, GramType& Ginv, PackedType& Gpacked, ArgType& args,
+                       CommType&& CommInfo, bool src_tiled = false, bool dst_tiled = false, bool shifted = false, double* rec = nullptr, int64_t m_glob = 0) {
+    capi_handle_t h = capital::handle();
+    gram_1d(src, src_tiled, m_loc, n, G, Gpacked, CommInfo);
     CRITTER_START(CQR::formR);
-    if (shifted) CAPITAL_CHECK(capi_dgram_equilibrate_shift(h, n, args.G.data(), n, m_glob, args.shift_scale, args.Dscale.data(), rec));
-    CAPITAL_CHECK(capi_dpotrf_trtri(h, n, args.G.data(), n, args.Ginv.data(), n));                                    // K8 + K9
-    if (rec) CAPITAL_CHECK(capi_dtri_rescale(h, n, args.G.data(), n, args.Ginv.data(), n, shifted ? args.Dscale.data() : nullptr, rec));
+    if (shifted) CAPITAL_CHECK(capi_dgram_equilibrate_shift(h, n, G.data(), n, m_glob, args.shift_scale, args.Dscale.data(), rec));
+    CAPITAL_CHECK(capi_dpotrf_trtri(h, n, G.data(), n, Ginv.data(), n));                                              // K8 + K9
+    if (rec) CAPITAL_CHECK(capi_dtri_rescale(h, n, G.data(), n, Ginv.data(), n, shifted ? args.Dscale.data() : nullptr, rec));
     if (src_tiled || dst_tiled)
-      CAPITAL_CHECK(capi_dtrmm_right_panel32(h, m_loc, n, 1.0, args.Ginv.data(), n, src, src_tiled ? 0 : m_loc, dst, dst_tiled ? 0 : m_loc));       // K5
+      CAPITAL_CHECK(capi_dtrmm_right_panel32(h, m_loc, n, 1.0, Ginv.data(), n, src, src_tiled ? 0 : m_loc, dst, dst_tiled ? 0 : m_loc));       // K5
     else
-      CAPITAL_CHECK(capi_dtrmm_oop(h, CAPI_RIGHT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, m_loc, n, 1.0, args.Ginv.data(), n, src, m_loc, dst, m_loc));  // K5
+      CAPITAL_CHECK(capi_dtrmm_oop(h, CAPI_RIGHT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, m_loc, n, 1.0, Ginv.data(), n, src, m_loc, dst, m_loc));  // K5
     CRITTER_STOP(CQR::formR);
   }
 
@@ -440,13 +397,13 @@ protected:
     // caller; each is written by one sweep and read twice by the next as a panel32 image -- one contiguous stream per pass instead of 256
     // column streams (CAPITAL_NO_PANEL32: column-major throughout, A/B).  The arithmetic, and so Q and R, are the same bit for bit.
     const bool q1_tiled = sweeps > 1 && n == 256 && m_loc % 32 == 0 && m_loc >= 64 * n && !getenv("CAPITAL_NO_PANEL32");
-    sweep_1d(A.data(), args.Q.data(), m_loc, n, args, CommInfo, false, q1_tiled, shifted > 0, rec, (int64_t)A.num_rows_global());
+    sweep_1d(A.data(), args.Q.data(), m_loc, n, args.G, args.Ginv, args.Gpacked, args, CommInfo, false, q1_tiled, shifted > 0, rec, (int64_t)A.num_rows_global());
     if (sweeps > 1) {
       args.R1._register_(n, n, 1, 1);
       capital::dev_copy(args.R1.data(), args.G.data(), n * n);                                                        // save_R_1d
       for (int64_t k = 1; k < sweeps; ++k) {
-        sweep_1d(args.Q.data(), args.Q.scratch(), m_loc, n, args, CommInfo, q1_tiled, q1_tiled && k + 1 < sweeps, k < shifted, rec ? rec + 4 * k : nullptr,
-                 (int64_t)A.num_rows_global());
+        sweep_1d(args.Q.data(), args.Q.scratch(), m_loc, n, args.G, args.Ginv, args.Gpacked, args, CommInfo, q1_tiled, q1_tiled && k + 1 < sweeps, k < shifted,
+                 rec ? rec + 4 * k : nullptr, (int64_t)A.num_rows_global());
         args.Q.swap();
         // R = R_k * (R_k-1 .. R1) (cacqr.hpp:185-187): Ginv is free again and receives the product
         CAPITAL_CHECK(capi_dtrmm_oop(h, CAPI_RIGHT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, n, n, 1.0, args.R1.data(), n, args.G.data(), n, args.Ginv.data(), n));

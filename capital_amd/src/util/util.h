@@ -117,6 +117,26 @@ public:
     CAPITAL_CHECK(capi_memcpy_d2h(capital::handle(), v, d, sizeof(double) * n));
     capital::dev_free(d);
   }
+
+  // a result block of r columns that a later call may ask for with another r: registered on first use, registered anew when r changed
+  template <typename MatrixType>
+  static void resize_columns(MatrixType& m, int64_t r, int64_t rows) {
+    if (m.filled() && m.num_columns_local() != r) m._destroy_();
+    m._register_(r, rows, 1, 1);
+  }
+
+  // The residual-norm tail of cholinv::solve and cacqr::least_squares: squared(j, rb, out) puts the squared norms of the columns [j, j + rb) of the
+  // residual into out (device, rb doubles), CAPI_TS_MAX_RHS columns a call; they are summed over `comm` (null: one rank), fetched and rooted.
+  template <typename MatrixType, typename F>
+  static std::vector<double> residual_norms(MatrixType& norm2, int64_t r, capi_comm_t comm, F&& squared) {
+    const int64_t W = CAPI_TS_MAX_RHS;
+    resize_columns(norm2, r, 1);
+    for (int64_t j = 0; j < r; j += W) squared(j, std::min(W, r - j), norm2.data() + j);
+    if (comm) CAPITAL_CHECK(capi_allreduce_sum(comm, norm2.data(), r));
+    std::vector<double> v = norm2.to_host();
+    for (double& x : v) x = std::sqrt(x);
+    return v;
+  }
 };
 
 #endif  // CAPITAL_UTIL_H_
