@@ -51,6 +51,8 @@ _SIGS = {
     "capi_dgesvj": [_i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(_int)],
     "capi_dpstrf": [_i64, _vp, _i64, _dbl, _vp, C.POINTER(_int)],
     "capi_drow_scatter": [_int, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64],
+    "capi_dpchol": [_i64, _vp, _i64, _dbl, _i64, _vp, _i64, _vp, _vp, C.POINTER(_int), C.POINTER(_dbl)],
+    "capi_dpchol_thresh": [_i64, _vp, _i64, _dbl, C.POINTER(_dbl)],
     "capi_get_info": [C.POINTER(_int)],
     "capi_reset_info": [],
     "capi_serialize": [_int, _int, _vp, _i64, _i64, _vp, _i64, _i64] + [_i64] * 8,

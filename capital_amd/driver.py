@@ -61,6 +61,8 @@ def bind(D):
     D.capital_cholinv_error_bounds.argtypes = [_vp, _i64, _dp, _dp, _dp]
     D.capital_cholinv_solve_expert.argtypes = [_vp, _i64, _dp, _dp, _dp, _int, _dp, _dp]
     D.capital_cholinv_update.argtypes = [_vp, _i64, _dp, _int]
+    D.capital_cholinv_factor_pivoted.argtypes = [_vp, _dbl, _i64, C.POINTER(_i64), _dp, _dp]
+    D.capital_cholinv_get_pivoted.argtypes = [_vp, _dp, C.POINTER(_int), _dp]
     D.capital_cacqr_create.argtypes = [_i64, _i64] + [_int] * 8
     D.capital_cacqr_create.restype = _vp
     D.capital_cacqr_set_A.argtypes = [_vp, _dp]
@@ -239,6 +241,42 @@ class Cholinv:
         if v.ndim != 2 or v.shape[0] != self.n or v.shape[1] < 1:
             raise DriverError(f"Cholinv.update: V must be {self.n} x r with r >= 1, got {v.shape}")
         _ck(self.D.capital_cholinv_update(self.p, v.shape[1], v.ctypes.data_as(_dp), -1 if downdate else 1), "update")
+
+    def factor_pivoted(self, rtol=0.0, max_rank=None):
+        """A ~= L L^T with L n x rank by a diagonally pivoted, partial Cholesky (cholesky::cholinv::factor_pivoted, one rank): for a symmetric matrix
+        that is only positive semidefinite or numerically low-rank -- where factor() raises -- or of which few columns are wanted; O(n rank^2).  It
+        stops where the largest remaining Schur diagonal entry is <= rtol trace(A) (rtol=0: LAPACK dpstrf's default n u max a_ii) or at max_rank
+        columns (None: min(n, 4096)).  Only A's upper triangle is read.  Returns (rank, resid_trace, thresh): resid_trace is the trace of A - L L^T,
+        its trace-norm error for a PSD A.  Afterwards L_pivoted(), piv() and schur_diagonal().  The factors of factor() are not touched.  Raises
+        DriverError at rank 0 (A is zero or not finite)."""
+        rk, tr, th = _i64(0), _dbl(0.0), _dbl(0.0)
+        self.pivot_rank = 0
+        _ck(self.D.capital_cholinv_factor_pivoted(self.p, float(rtol), 0 if max_rank is None else int(max_rank), C.byref(rk), C.byref(tr), C.byref(th)),
+            "factor_pivoted")
+        self.pivot_rank = rk.value
+        return rk.value, tr.value, th.value
+
+    def _get_pivoted(self, what):
+        rank = getattr(self, "pivot_rank", 0)
+        if rank < 1:
+            raise DriverError("Cholinv: factor_pivoted() has not run or did not succeed")
+        out = {"L": np.zeros((self.n, rank), order="F"), "piv": np.zeros(self.n, dtype=np.int32), "d": np.zeros(self.n)}[what]
+        _ck(self.D.capital_cholinv_get_pivoted(self.p, out.ctypes.data_as(_dp) if what == "L" else None,
+                                               out.ctypes.data_as(C.POINTER(_int)) if what == "piv" else None,
+                                               out.ctypes.data_as(_dp) if what == "d" else None), "get_pivoted")
+        return out
+
+    def L_pivoted(self):
+        """L of the last factor_pivoted(), n x rank, in A's own row ordering: column j belongs to row piv()[j], rows chosen before it are zero there"""
+        return self._get_pivoted("L")
+
+    def piv(self):
+        """the rows factor_pivoted() chose, in order, then the others ascending: a permutation of 0 .. n - 1"""
+        return self._get_pivoted("piv").astype(np.int64)
+
+    def schur_diagonal(self):
+        """diag(A - L L^T) as factor_pivoted() carried it: the remaining Schur diagonal of the rows not chosen, 0 for the chosen ones"""
+        return self._get_pivoted("d")
 
     def _get(self, which):
         out = np.zeros((self.n_loc, self.n_loc), order="F")

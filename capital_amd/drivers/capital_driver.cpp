@@ -49,6 +49,8 @@ struct cholinv_problem {
   virtual void rcond(double* rcond, double* anorm1, int* applies) = 0;
   virtual void error_bounds(int64_t r, const double* B_host, double* ferr_host, double* berr_host, int* applies) = 0;
   virtual void update(int64_t r, const double* V_host, int sign) = 0;
+  virtual void factor_pivoted(double rtol, int64_t max_rank, int64_t* rank, double* resid_trace, double* thresh) = 0;
+  virtual void get_pivoted(double* L_host, int* piv_host, double* d_host) = 0;
 };
 
 template <class Alg>
@@ -119,6 +121,24 @@ struct cholinv_impl : cholinv_problem {
     MatrixType V(r, A.num_rows_global(), 1, 1);
     V.from_host(V_host);
     Alg::update(A, V, pack, grid, sign);
+  }
+  // A ~= L L^T by the pivoted partial Cholesky; rtol 0: LAPACK's default threshold, max_rank 0: min(n, CAPI_PCHOL_MAX_RANK)
+  void factor_pivoted(double rtol, int64_t max_rank, int64_t* rank, double* resid_trace, double* thresh) override {
+    if (max_rank < 0) throw std::invalid_argument("cholinv factor_pivoted: max_rank >= 0 expected (0: the default)");
+    pack.pivot_rtol = rtol;
+    pack.pivot_max_rank = max_rank;
+    // (the results are handed out whether or not the call throws at rank 0)
+    auto hand_out = [&] { if (rank) *rank = pack.pivot_rank; if (resid_trace) *resid_trace = pack.resid_trace; if (thresh) *thresh = pack.pivot_thresh; };
+    try { Alg::factor_pivoted(A, pack, grid); } catch (...) { hand_out(); throw; }
+    hand_out();
+  }
+  // of the last factor_pivoted(): L n x rank column-major, piv n ints, d n doubles (each may be NULL)
+  void get_pivoted(double* L_host, int* piv_host, double* d_host) override {
+    if (pack.pivot_rank < 1 || !pack.Lp.filled() || pack.pivl.empty()) throw std::logic_error("cholinv get_pivoted: factor_pivoted() has not run or did not succeed");
+    const int64_t n = A.num_rows_local();
+    if (L_host) CAPITAL_CHECK(capi_memcpy_d2h(capital::handle(), L_host, pack.Lp.data(), sizeof(double) * (size_t)(n * pack.pivot_rank)));
+    if (piv_host) std::memcpy(piv_host, pack.pivl.data(), sizeof(int) * (size_t)n);
+    if (d_host) fetch(pack.Dres, d_host);
   }
 };
 
@@ -341,6 +361,15 @@ int capital_cholinv_solve_expert(void* p, int64_t r, const double* B_host, doubl
 // capital_drv_last_error when a downdate leaves the matrix not positive definite: A is then unchanged and the factors are invalid until the next factor.
 int capital_cholinv_update(void* p, int64_t r, const double* V_host, int sign) {
   return guarded([&] { ((cholinv_problem*)p)->update(r, V_host, sign); });
+}
+// A ~= L L^T, L n x rank, by a diagonally pivoted partial Cholesky (cholesky::cholinv::factor_pivoted; one rank): for a matrix that is only positive
+// semidefinite or numerically low-rank, where capital_cholinv_factor fails.  rtol: stop where the largest remaining Schur diagonal entry is <= rtol trace(A)
+// (0: LAPACK dpstrf's default); max_rank: 0 = min(n, CAPI_PCHOL_MAX_RANK).  The factors of capital_cholinv_factor, if any, are not touched.
+int capital_cholinv_factor_pivoted(void* p, double rtol, int64_t max_rank, int64_t* rank, double* resid_trace, double* thresh) {
+  return guarded([&] { ((cholinv_problem*)p)->factor_pivoted(rtol, max_rank, rank, resid_trace, thresh); });
+}
+int capital_cholinv_get_pivoted(void* p, double* L_host /* n x rank */, int* piv_host /* n */, double* d_host /* n */) {
+  return guarded([&] { ((cholinv_problem*)p)->get_pivoted(L_host, piv_host, d_host); });
 }
 int capital_cholinv_destroy(void* p) { return guarded([&] { capital::sync(); delete (cholinv_problem*)p; }); }
 

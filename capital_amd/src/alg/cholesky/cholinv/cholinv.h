@@ -37,6 +37,9 @@
 #pragma weak capi_dchud
 #pragma weak capi_dchud_inv
 #pragma weak capi_dchud_log_bytes
+// .. and the pivoted partial factorization: without them factor_pivoted() refuses and everything else runs as before
+#pragma weak capi_dpchol
+#pragma weak capi_dpchol_thresh
 
 namespace cholesky {
 
@@ -109,6 +112,17 @@ public:
     matmult::arena ops;
     // update(): the step of the last failed downdate (0: none)
     int update_info = 0;
+    // factor_pivoted().  Input: pivot_rtol -- the factorization stops where the largest remaining Schur diagonal entry is <= pivot_rtol trace(A); 0:
+    // LAPACK dpstrf's default n u max_i a_ii; pivot_max_rank -- the most columns of L, 0: min(n, CAPI_PCHOL_MAX_RANK).  Results: Lp (n x max_rank, the
+    // first pivot_rank columns valid, in A's own row ordering), pivl (host) / PivL (device: n ints in the first (n + 1) / 2 doubles): the chosen rows in
+    // order, then the others ascending; Dres (n): the remaining Schur diagonal, 0 for a chosen row; resid_trace: its sum, for a PSD A the trace norm
+    // of A - Lp Lp^T; pivot_thresh: the threshold the call stopped at.  None of these is read by factor(), solve(), condition() or update().
+    double pivot_rtol = 0.0;
+    int64_t pivot_max_rank = 0;
+    matrix<ScalarType, DimensionType, rect> Lp, PivL, Dres;
+    std::vector<int> pivl;
+    int64_t pivot_rank = 0;
+    double resid_trace = 0.0, pivot_thresh = 0.0;
   };
 
   template <typename MatrixType, typename ArgType, typename CommType>
@@ -453,6 +467,45 @@ public:
       throw std::domain_error("cholinv::update: the " + std::string(sign > 0 ? "updated" : "downdated") + " matrix is not positive definite (step " +
                               std::to_string(info) + " of " + std::to_string(n) + (r > W ? ", columns from " + std::to_string(bad_block) + " of V" : std::string()) +
                               "); A is unchanged, R and Rinv are not valid: factor() again");
+  }
+
+  // A ~= Lp Lp^T by a diagonally pivoted, PARTIAL Cholesky (capi_dpchol), for a symmetric A that is only positive SEMIdefinite or numerically low-rank --
+  // where factor() throws on the first non-positive pivot -- or of which k << n columns are wanted: O(n k^2), not O(n^3).  ONE rank.  Swap-free: Lp
+  // (n x max_rank) is in A's own row ordering, column j belongs to the row args.pivl[j]; rows chosen before step j are exactly zero in column j.  It stops
+  // at rank k where the largest remaining Schur diagonal entry is <= args.pivot_thresh = pivot_rtol trace(A) (pivot_rtol == 0: LAPACK dpstrf's default
+  // n u max_i a_ii), or at max_rank = args.pivot_max_rank (0: min(n, CAPI_PCHOL_MAX_RANK)).  args.Dres is the Schur diagonal that remains and
+  // args.resid_trace its sum: for a PSD A the trace norm of A - Lp Lp^T.  Like factor(), only A's upper triangle is read.
+  // Independent of factor(): R, R^-1, `factored` and A are neither read nor changed; solve(), condition() and update() behave afterwards as before.
+  // std::domain_error at rank 0 (A is zero or not finite), as qr::cacqr::factor_pivoted.
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void factor_pivoted(const MatrixType& A, ArgType& args, CommType&& CommInfo) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::factor_pivoted takes a rect-structured input block");
+    if (CommInfo.size > 1) throw std::logic_error("cholinv::factor_pivoted is built for one rank: on a grid the matrix is element-cyclic");
+    if (!&capi_dpchol || !&capi_dpchol_thresh) throw std::logic_error("cholinv: this C-ABI library has no capi_dpchol: no pivoted factorization");
+    const int64_t n = A.num_rows_local();
+    const int64_t cap = std::min<int64_t>(n, CAPI_PCHOL_MAX_RANK), kmax = args.pivot_max_rank == 0 ? cap : args.pivot_max_rank;
+    if (n < 1 || A.num_columns_local() != n || kmax < 1 || kmax > cap || !(args.pivot_rtol >= 0.0))
+      throw std::invalid_argument("cholinv::factor_pivoted: A n x n with n >= 1, 0 <= pivot_max_rank <= min(n, CAPI_PCHOL_MAX_RANK), pivot_rtol >= 0");
+    args.pivot_rank = 0;
+    args.resid_trace = args.pivot_thresh = 0.0;
+    args.pivl.clear();
+    CRITTER_START(CI::factor_pivoted);
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    util::resize_columns(args.Lp, kmax, n);
+    args.PivL._register_(1, (n + 1) / 2, 1, 1);
+    args.Dres._register_(1, n, 1, 1);
+    int* const piv = reinterpret_cast<int*>(args.PivL.data());
+    const double tol = args.pivot_rtol == 0.0 ? -1.0 : args.pivot_rtol;
+    int rank = 0;
+    CAPITAL_CHECK(capi_dpchol_thresh(h, n, A.data(), n, tol, &args.pivot_thresh));
+    CAPITAL_CHECK(capi_dpchol(h, n, A.data(), n, tol, kmax, args.Lp.data(), n, piv, args.Dres.data(), &rank, &args.resid_trace));
+    args.pivl.resize((size_t)n);
+    CAPITAL_CHECK(capi_memcpy_d2h(h, args.pivl.data(), piv, sizeof(int) * (size_t)n));
+    args.pivot_rank = rank;
+    CRITTER_STOP(CI::factor_pivoted);
+    if (rank == 0)
+      throw std::domain_error("cholinv::factor_pivoted: numerical rank 0: no diagonal entry exceeds the threshold (A is zero or not finite)");
   }
 
   // ---- TRSM mode -----------------------------------------------------------------------------------------------------------

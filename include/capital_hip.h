@@ -295,6 +295,35 @@ int capi_dpstrf(capi_handle_t h, int64_t n, double* G, int64_t ldg, double tol, 
  * at Q and R.  tri = 1 takes only S's upper triangle: entries below the diagonal count as zero and are not read.  Serves M = P(:, 0:k) R11^-1 and the
  * basic least-squares solution X = P [Y; 0].  D must not alias S.  k == 0: zeros alone; n == 0 or ncols == 0: nothing.  No workspace. */
 int capi_drow_scatter(capi_handle_t h, int tri, int64_t k, int64_t ncols, int64_t n, const double* S, int64_t lds, const int* piv, double* D, int64_t ldd);
+/* ---- diagonally pivoted, PARTIAL Cholesky of a symmetric positive semidefinite or numerically low-rank matrix of any order, A ~= L L^T with L n x k
+ * (cholesky::cholinv::factor_pivoted: what a caller has where capi_dpotrf refuses, or where k << n columns are wanted; O(n k^2), not O(n^3)).
+ * Not in the reference: cholinv.hpp stops at R and R^-1.  A is n x n, column-major, lda >= n; only its UPPER triangle, diagonal included, is read --
+ * what lies below may be NaN -- and A is never written.  L is n x max_rank, column-major, ldl >= n; piv and d are DEVICE arrays of n ints and n doubles.
+ * 1 <= n < 2^31, 1 <= max_rank <= min(n, CAPI_PCHOL_MAX_RANK); anything else, a null pointer, lda < n, ldl < n or a NaN tol returns CAPI_EINVAL before
+ * any launch, with nothing touched.  Pointers aligned to 8 bytes (piv to 4).  The handle's info word is not touched.
+ * Swap-free: the factor stays in A's own ordering.  With d = diag(A) at the start, step j = 0, 1, .. takes p = the FIRST index of the largest remaining
+ * d_i (ties to the smaller index, a NaN counts as -inf, chosen indices are out of the running) and stops unless d_p > thresh -- written so that a
+ * NaN compares false and stops.  Otherwise, for the rows i not yet chosen, L(i, j) = (A(i, p) - sum_{l < j} L(i, l) L(p, l)) / sqrt(d_p), l ascending,
+ * A(i, p) taken from the upper triangle; L(i, j) = 0 exactly for the rows chosen before; L(p, j) = sqrt(d_p); d_i <- fl(d_i - fl(L(i, j)^2)), the
+ * product and the difference rounded one after the other, so that d can be recomputed from L bit for bit.
+ * thresh = tol * trace(A), as in capi_dpstrf; tol < 0: LAPACK dpstrf's default n u max_i a_ii, u = 2^-53.
+ * On exit *rank_host = k, 0 <= k <= max_rank; columns < k of L are written, columns >= k and the padding rows of L are NOT; piv[0 .. k) holds the chosen
+ * indices in order and piv[k .. n) the others ascending, so piv is always a permutation; d[i] is the remaining Schur diagonal of a row that was not
+ * chosen and 0 for a chosen one; *resid_trace_host is the sum of d over the rows not chosen -- for a PSD A the trace norm of A - L L^T.
+ * Non-finite input ends the call like any other (every loop has a trip count fixed by n and max_rank): CAPI_OK, 0 <= k <= max_rank, piv a
+ * permutation, the values unspecified.
+ * Method (csrc/pchol_f64.hip): one launch per step over ceil(n / 256) workgroups, a thread owns a row; the pivot row L(p, 0 .. j) is staged in LDS
+ * once per workgroup; a workgroup ends its step with its own (value, index) candidate for the next pivot, and every workgroup of the next launch
+ * reduces those ceil(n / 256) candidates -- no workgroup reads the whole of d.  A stop sets a device flag; later launches read it at entry and return.
+ * The host enqueues the steps in rounds of 64 and reads the flag once per round.  Ordered by kernel boundaries on the handle's stream alone: no
+ * cooperative launch, no device-side waiting, no atomics; sums have a fixed order: two calls on the same bits give identical bytes.
+ * Workspace, of the handle's own: 4 n + 64 ceil(n / 256) + 32 bytes. */
+enum { CAPI_PCHOL_MAX_RANK = 4096 };
+int capi_dpchol(capi_handle_t h, int64_t n, const double* A, int64_t lda, double tol, int64_t max_rank, double* L, int64_t ldl, int* piv, double* d,
+                int* rank_host, double* resid_trace_host);
+/* The threshold that capi_dpchol(h, n, A, lda, tol, ..) stops at, bit for bit (the same kernels sum the same diagonal in the same order).  Not in the
+ * reference: cholinv.hpp stops at R and R^-1.  Reads A's diagonal alone; CAPI_EINVAL as there, with nothing touched. */
+int capi_dpchol_thresh(capi_handle_t h, int64_t n, const double* A, int64_t lda, double tol, double* thresh_host);
 /* LAPACKE_dgeqrf / LAPACKE_dorgqr behind lapack::engine::_geqrf / _orgqr (lapack/interface.hpp:60-88; the reference has
  * the slots but no caller -- CholeskyQR2 is its QR).  Householder QR, LAPACK storage: R in the upper triangle, the
  * reflectors v_j (unit first entry implied) below it, tau[min(m,n)] on the DEVICE.  capi_dorgqr overwrites A (m x n,
