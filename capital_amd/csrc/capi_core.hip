@@ -35,7 +35,7 @@ static int capi_create_fill(capi_handle_s* h, int device, void* stream, bool own
   CAPI_HIP_CHECK(h, hipSetDevice(device));
   if (own) {
     // the handle's own compute stream carries the factorisation's latency-bound chain: highest priority, so that its
-    // workgroups are preferred over the bulk streams' wherever the dispatcher arbitrates
+    // workgroups are preferred over other streams' of the process wherever the dispatcher arbitrates
     int least = 0, greatest = 0;
     CAPI_HIP_CHECK(h, hipDeviceGetStreamPriorityRange(&least, &greatest));
     CAPI_HIP_CHECK(h, hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, getenv("CAPI_MAIN_PRIO_NORMAL") ? 0 : greatest));
@@ -192,36 +192,15 @@ int capi_reset_info(capi_handle_t h) {
 int capi_stream_select(capi_handle_t h, int which) {
   CAPI_REQUIRE(h, h && which >= 0 && which < capi_handle_s::NSTREAMS, "stream index");
   if (!h->streams[0]) h->streams[0] = h->stream;
-  if (which >= 1 && !h->streams[which]) {
+  if (which == 1 && !h->streams[1]) {
     CAPI_HIP_CHECK(h, hipSetDevice(h->device));
-    if (which == 1) {
-      // The communication stream carries RCCL's kernels (and packing copies): few, short-lived or few-workgroup launches that a chunk
-      // pipeline is waiting for.  Highest priority, like the compute stream: whenever the dispatcher has a free slot and both queues hold
-      // work, theirs goes first -- a tile launch of thousands of workgroups behind it loses nothing (CAPI_COMM_PRIO_NORMAL: default priority,
-      // A/B; measured in profiles/r4_overlap_*: what decides is whether a slot is free at all, see capi_reserve_cus).
-      int least = 0, greatest = 0;
-      CAPI_HIP_CHECK(h, hipDeviceGetStreamPriorityRange(&least, &greatest));
-      CAPI_HIP_CHECK(h, hipStreamCreateWithPriority(&h->streams[1], hipStreamNonBlocking, getenv("CAPI_COMM_PRIO_NORMAL") ? 0 : greatest));
-    } else {
-      // Bulk streams run long MFMA tile kernels beside the compute stream's latency-bound chain: lowest priority.
-      // A tile workgroup owns a whole CU (512 threads x 256 VGPRs) and the workgroups of one launch finish in rounds, so
-      // the chain's kernels mostly start when a round ends.  CAPITAL_BULK_CUS = n (< number of CUs) instead keeps the
-      // bulk streams off the last CUs with a CU mask (mask bit b = CU b/8 of XCD b%8); measured at n = 32768: the chain
-      // then runs freely, but the bulk launches lose their fit to 256 CUs (8 rounds become 9.1 -> 10) and the step time is
-      // the same, so the default is no mask.
-      const char* e = getenv("CAPITAL_BULK_CUS");
-      int bulk = e ? atoi(e) : 0;
-      if (bulk > 0 && bulk < h->num_cu) {
-        uint32_t mask[16] = {0};
-        for (int b = 0; b < bulk && b < 512; ++b) mask[b >> 5] |= 1u << (b & 31);
-        CAPI_HIP_CHECK(h, hipExtStreamCreateWithCUMask(&h->streams[which], (uint32_t)((h->num_cu + 31) / 32), mask));
-        h->cu_of[which] = bulk;
-      } else {
-        int least = 0, greatest = 0;
-        CAPI_HIP_CHECK(h, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        CAPI_HIP_CHECK(h, hipStreamCreateWithPriority(&h->streams[which], hipStreamNonBlocking, least));
-      }
-    }
+    // The communication stream carries RCCL's kernels (and packing copies): few, short-lived or few-workgroup launches that a chunk
+    // pipeline is waiting for.  Highest priority, like the compute stream: whenever the dispatcher has a free slot and both queues hold
+    // work, theirs goes first -- a tile launch of thousands of workgroups behind it loses nothing (CAPI_COMM_PRIO_NORMAL: default priority,
+    // A/B; measured in profiles/r4_overlap_*: what decides is whether a slot is free at all, see capi_reserve_cus).
+    int least = 0, greatest = 0;
+    CAPI_HIP_CHECK(h, hipDeviceGetStreamPriorityRange(&least, &greatest));
+    CAPI_HIP_CHECK(h, hipStreamCreateWithPriority(&h->streams[1], hipStreamNonBlocking, getenv("CAPI_COMM_PRIO_NORMAL") ? 0 : greatest));
   }
   h->stream = h->streams[which];
   h->cur = which;

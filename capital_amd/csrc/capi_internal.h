@@ -10,27 +10,26 @@ struct capi_handle_s {
   int device = 0;
   hipStream_t stream = nullptr;
   bool owns_stream = false;
-  // streams[0] = compute (== the handle's primary stream), streams[1] = communication / packing, streams[2..] = bulk
-  // trailing updates that run beside the factorisation's latency-bound chain (lowest priority); created on first select
-  static constexpr int NSTREAMS = 4;
-  hipStream_t streams[NSTREAMS] = {nullptr, nullptr, nullptr, nullptr};
+  // streams[0] = compute (== the handle's primary stream), streams[1] = communication / packing; created on first select
+  static constexpr int NSTREAMS = 2;
+  hipStream_t streams[NSTREAMS] = {nullptr, nullptr};
   int cur = 0;                    // index of the selected stream
-  int cu_of[NSTREAMS] = {0, 0, 0, 0};   // CUs a stream may use when it carries a CU mask (0 = all): launch heuristics count rounds with it
+  int cu_of[NSTREAMS] = {0, 0};   // CUs a stream may use when it carries a CU mask (0 = all): launch heuristics count rounds with it
   hipEvent_t* events = nullptr;   // 1024 lazily created slots
   // private workspace (in-place trmm staging, split-K slabs, potrf panels); grows on demand.  One per stream index:
   // reuse is stream-ordered, so work on different streams must not share a block
-  void* ws[NSTREAMS] = {nullptr, nullptr, nullptr, nullptr};
-  size_t ws_bytes[NSTREAMS] = {0, 0, 0, 0};
+  void* ws[NSTREAMS] = {nullptr, nullptr};
+  size_t ws_bytes[NSTREAMS] = {0, 0};
   // second, independent scratch block (diagonal-block inverses, recursion temporaries)
-  void* ws2[NSTREAMS] = {nullptr, nullptr, nullptr, nullptr};
-  size_t ws2_bytes[NSTREAMS] = {0, 0, 0, 0};
+  void* ws2[NSTREAMS] = {nullptr, nullptr};
+  size_t ws2_bytes[NSTREAMS] = {0, 0};
   // third block: clean copies of small triangular operands (tall right-TRMM); never aliases what callers keep in ws / ws2
-  void* ws3[NSTREAMS] = {nullptr, nullptr, nullptr, nullptr};
-  size_t ws3_bytes[NSTREAMS] = {0, 0, 0, 0};
+  void* ws3[NSTREAMS] = {nullptr, nullptr};
+  size_t ws3_bytes[NSTREAMS] = {0, 0};
   // fourth block: the tall QR paths' panels (CholeskyQR2 + Householder reconstruction keeps two m x n images beside the BLAS /
   // LAPACK calls it makes, which use ws / ws2 / ws3 themselves).  hipMalloc of tens of GiB takes hundreds of ms: kept between calls
-  void* ws4[NSTREAMS] = {nullptr, nullptr, nullptr, nullptr};
-  size_t ws4_bytes[NSTREAMS] = {0, 0, 0, 0};
+  void* ws4[NSTREAMS] = {nullptr, nullptr};
+  size_t ws4_bytes[NSTREAMS] = {0, 0};
   // device-side LAPACK info word (0 ok, >0 first bad pivot, 1-based) + pinned host mirror
   int* d_info = nullptr;
   int* h_info = nullptr;

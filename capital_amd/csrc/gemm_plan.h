@@ -226,10 +226,10 @@ inline Plan plan(const Product& p, const Device& dev, const Modes& mode, const O
   // product do equal work, so the round boundary costs nothing measurable.  Triangular outputs were tried the same way (8 x 8
   // super-blocks of the triangle, 8 per round; bit 1 of rounds_mode): FETCH of the n = 32768 step 310 -> 263 GB only, dsyrk 16384
   // 62.6 -> 64.2 ms, step 237 -> 242 ms (partial rounds, diagonal super-blocks with 36 live tiles): not kept.  TRMM tiles have unequal
-  // k-ranges and keep the longest-first free-running order.  OFF by default (CAPI_ROUNDS=1 turns it on): inside cholinv the plain
-  // products are the lookahead's rectangles only -- the step's fabric traffic falls by 5 % (3625 -> 3437 GB at n = 65536), its time
-  // does not change, and the per-launch durations the roofline is computed from stretch, because the round launches of a low-priority
-  // bulk stream queue behind the chain's kernels at every boundary (0.876 -> 0.825 on the same box).
+  // k-ranges and keep the longest-first free-running order.  OFF by default (CAPI_ROUNDS=1 turns it on; cholinv::factor
+  // turns rounds on for its own call, capi_set_launch_rounds): when this was measured the only plain products inside cholinv were the
+  // rectangles of a since-removed second-stream schedule -- the step's fabric traffic fell by 5 % (3625 -> 3437 GB at n = 65536), its
+  // time did not change, and the per-launch durations the roofline was computed from stretched (0.876 -> 0.825 on the same box).
   // (The 256-column block launches of a tall right-TRMM were tried the same way: a round there is 512 tiles of K <= 1024, ~0.15 ms, and
   //  the launch boundaries cost 11 %: 35.1 -> 39.2 ms at m = 2^21, n = 1024.)
   const int per_round = 2 * ncu;

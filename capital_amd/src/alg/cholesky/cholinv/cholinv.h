@@ -87,13 +87,10 @@ public:
     // LAPACK info of the factorisation (the reference drops it, lapack/interface.hpp:39,54): 0, or the 1-based position,
     // inside the first diagonal block that failed, of the first non-positive pivot.  factor() throws std::domain_error then.
     int potrf_info = 0;
-    bool zeroed = false;
     // top-level overlap state: the input's right part is copied, and the finished left part packed, on the second stream
     const double* input = nullptr;
     DimensionType early_split = 0;
     DimensionType input_lead = 0;       // > 0: only this leading block of the input's left half was copied on the compute stream
-    // trailing updates currently running beside the recursion on the bulk streams (single-GPU lookahead)
-    int la_depth = 0;
     // solve(): `factored` -- the last factor() came back with valid factors; top_split -- the order h1 of the leading block when the top level
     // of the recursion split (0: it did not).  With complete_inv == 0 that is where R^-1 has its unformed block R^-1_12.
     bool factored = false, factored_trsm = false;     // factored_trsm: the mode (solve_with_trsm) that factor() ran in
@@ -140,42 +137,19 @@ public:
     CAPITAL_CHECK(capi_stream_select(capital::handle(), 0));    // (a call that threw mid-way may have left another stream selected)
     CAPITAL_CHECK(capi_reset_info(capital::handle()));
     args.potrf_info = 0;
-    args.R._register_(A.num_columns_global(), A.num_rows_global(), CommInfo.d, CommInfo.d);
-    args.Rinv._register_(A.num_columns_global(), A.num_rows_global(), CommInfo.d, CommInfo.d);
     constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
-    if (packed) {
-      args.Rfull._register_(A.num_columns_global(), A.num_rows_global(), CommInfo.d, CommInfo.d);
-      args.Rinvfull._register_(A.num_columns_global(), A.num_rows_global(), CommInfo.d, CommInfo.d);
-    }
-    double* R = packed ? args.Rfull.data() : (double*)args.R.data();
-    double* Ri = packed ? args.Rinvfull.data() : (double*)args.Rinv.data();
+    // cholinv.hpp:13: the upper triangle of the input becomes the working R; the rest of R and all of R^-1 are zero (working_images)
+    const working w = working_images(A, args, CommInfo, true);
+    double *const R = w.R, *const Ri = w.Rinv;
     const U ld = localDimension;
-    // cholinv.hpp:13: the upper triangle of the input becomes the working R; the rest of R and all of R^-1 are zero
-    // Freshly registered blocks are zero (matrix::allocate) and nothing below ever stores a non-zero where the result
-    // must be zero (strictly-lower parts; the skipped R^-1_12 at the top level), so later calls do not re-zero 2 n_loc^2.
-    if (!args.zeroed) {
-      capital::dev_zero(R, ld * ld);
-      capital::dev_zero(Ri, ld * ld);
-      args.zeroed = true;
-    }
-    // base-case size rule, cholinv.hpp:15-18
-    U bcDimLocal = (U)(CommInfo.c * CommInfo.d);
-    U bcMult = args.bc_mult_dim;
-    if (bcMult < 0) { bcMult = -bcMult; for (U i = 0; i < bcMult; ++i) bcDimLocal *= 2; } else { for (U i = 0; i < bcMult; ++i) bcDimLocal /= 2; }
-    bcDimLocal = std::max<U>(1, bcDimLocal);
-    bcDimLocal = std::min<U>(localDimension, bcDimLocal);
-    bcDimLocal = localDimension / bcDimLocal;
-    args.localDimension = args.trueLocalDimension = localDimension;
-    args.globalDimension = args.trueGlobalDimension = globalDimension;
-    args.bcDimension = (U)CommInfo.d * bcDimLocal;
-    args.num_base_cases = args.num_levels = 0;
+    set_dimensions(A, args, CommInfo);
 
     // Only the leading block is needed to start the left half's recursion (a chain of latency-bound kernels): the
     // rest of the input follows on the second stream and is awaited just before the top level's R12 product.
     const U h1 = localDimension >> args.split;
     args.input = A.data();
     args.early_split = 0;
-    const bool will_split = !(((localDimension * (U)CommInfo.d) <= args.bcDimension) || (h1 < args.split));   // cholinv.hpp:93
+    const bool will_split = splits(args, localDimension, (U)CommInfo.d);
     args.input_lead = 0;
     args.top_split = will_split ? h1 : 0;
     if (will_split && h1 > 0 && h1 < ld) {
@@ -208,20 +182,20 @@ public:
     // deepest concurrent need: panels + partial sums of the top level, or the aggregated base case
     const bool single = (CommInfo.d == 1 && CommInfo.c == 1);
     // the large launches go out one resident round at a time: same time, half the L2-to-fabric traffic (on grids: bandwidth the collectives'
-    // copy kernels share).  On one GPU the rounds of the lookahead's bulk streams interleave with each other and with the chain -- harmless,
-    // but stream-ordered event brackets around a round then also contain its neighbours, which is why the roofline figure is taken from the
-    // kernels' own interval stamps (capi_prof_collect_intervals).  CAPITAL_NO_LAUNCH_ROUNDS: one launch per product.
+    // copy kernels share).  The roofline figure is taken from the kernels' own interval stamps, which stay right when another stream (the packing,
+    // a grid's collectives) runs beside a round, not from stream-ordered event brackets (capi_prof_collect_intervals).
+    // CAPITAL_NO_LAUNCH_ROUNDS: one launch per product.
     capital::launch_rounds_scope rounds(true);
     const U h = localDimension - (localDimension >> args.split);
     const U agg = args.bcDimension;
-    // (single GPU: the R12 copies of nested levels stay live while their trailing updates run beside the recursion: h^2 (1 + 1/4 + ...))
+    // (single GPU: one split1 x split2 block is live at a time -- W of step 2, released before step 4, then W2 of step 5 -- and
+    //  split1 split2 <= h^2 at every level; the single-GPU trmm and syrk of summa.h take nothing from the arena)
     // (grids: the update's W, its exchanged copy + staging, two panels, the partial sums + their packed image, relay space and the landing
     //  half of the multi-path pair transfers, per-chunk copies of a pipelined multiply)
     //  (the K-sliced grids, d == 1, broadcast and relay nothing: 8 h^2 as in round 2 -- at n = 65536 on 1 x 1 x 2 h^2 is 8 GiB)
-    int64_t need = single ? (int64_t)h * h + (int64_t)h * h / 3 + 1024 : (int64_t)(CommInfo.d == 1 ? 8 : 12) * h * h + 4 * (int64_t)agg * agg + 4096;
+    int64_t need = single ? (int64_t)h * h + 1024 : (int64_t)(CommInfo.d == 1 ? 8 : 12) * h * h + 4 * (int64_t)agg * agg + 4096;
     args.work.reserve(need);
 
-    args.la_depth = 0;
     invoke(args, CommInfo, R, Ri, ld, (U)0, localDimension, globalDimension);
 
     if (packed) {
@@ -242,7 +216,7 @@ public:
       // the call only what the caller asked for stays resident (n = 65536 on one GPU: 96 GiB instead of 171 GiB beside A).
       capital::sync();
       args.work.release();
-      if (packed) { args.Rfull._destroy_(); args.Rinvfull._destroy_(); args.zeroed = false; }
+      if (packed) { args.Rfull._destroy_(); args.Rinvfull._destroy_(); }
     }
     CRITTER_STOP(CI::factor);
     // one 4-byte read behind the whole launch chain: a non-SPD input must not come back as NaN factors with status OK
@@ -521,19 +495,10 @@ public:
     CAPITAL_CHECK(capi_stream_select(h, 0));
     CAPITAL_CHECK(capi_reset_info(h));
     args.potrf_info = 0;
-    args.R._register_(A.num_columns_global(), A.num_rows_global(), CommInfo.d, CommInfo.d);
     constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
-    if (packed) args.Rfull._register_(A.num_columns_global(), A.num_rows_global(), CommInfo.d, CommInfo.d);
-    double* R = packed ? args.Rfull.data() : (double*)args.R.data();
-    if (!args.zeroed) { capital::dev_zero(R, ld * ld); args.zeroed = true; }
+    double* const R = working_images(A, args, CommInfo, false).R;
     CAPITAL_CHECK(capi_dlacpy(h, 1, ld, ld, A.data(), ld, R, ld));                                   // cholinv.hpp:13
-    U bcDimLocal = (U)(CommInfo.c * CommInfo.d), bcMult = args.bc_mult_dim;                           // cholinv.hpp:15-18
-    if (bcMult < 0) { bcMult = -bcMult; for (U i = 0; i < bcMult; ++i) bcDimLocal *= 2; } else { for (U i = 0; i < bcMult; ++i) bcDimLocal /= 2; }
-    bcDimLocal = ld / std::min<U>(ld, std::max<U>(1, bcDimLocal));
-    args.localDimension = args.trueLocalDimension = ld;
-    args.globalDimension = args.trueGlobalDimension = A.num_rows_global();
-    args.bcDimension = (U)CommInfo.d * bcDimLocal;
-    args.num_base_cases = args.num_levels = 0;
+    set_dimensions(A, args, CommInfo);
     if (CommInfo.d == 1) {
       potrf_rec(args, R, ld, (U)0, ld);                 // (d == 1, c > 1: every layer holds the whole matrix and factors it)
     } else {
@@ -569,7 +534,7 @@ public:
     const int64_t d = (int64_t)t.d, P = (int64_t)t.size, me = (int64_t)t.x + d * (int64_t)t.y;
     const U split1 = dim >> args.split;
     double* R11 = R + start + start * ld;
-    if (((dim * (U)t.d) <= args.bcDimension) || (split1 < args.split)) {                              // cholinv.hpp:93
+    if (!splits(args, dim, (U)t.d)) {
       CRITTER_START(CI::factor_diag);
       const int64_t L = dim, agg = L * d;
       const int64_t span = ((start + dim) != args.trueLocalDimension) ? agg : agg - (args.trueLocalDimension * d - args.trueGlobalDimension);
@@ -639,7 +604,7 @@ public:
     capi_handle_t h = capital::handle();
     const U split1 = dim >> args.split;
     double* R11 = R + start + start * ld;
-    if (dim <= args.bcDimension || split1 < args.split) {                                            // cholinv.hpp:93
+    if (!splits(args, dim, (U)1)) {
       CRITTER_START(CI::factor_diag);
       CAPITAL_CHECK(capi_dpotrf(h, CAPI_UPPER, dim, R11, ld));
       CRITTER_STOP(CI::factor_diag);
@@ -826,26 +791,45 @@ private:
 
   // event slots of the top-level overlap (matmult::summa's pipe uses slots below 1000)
   static constexpr int EV_INPUT_HEAD = 1020, EV_INPUT_REST = 1021, EV_TOP_R12 = 1022, EV_EARLY_PACK = 1023, EV_INPUT_MID = 1019;
-  // lookahead (single GPU): slot + depth; the bulk streams are stream indices LA_STREAM0 + depth
   static constexpr int EV_BC_POTRF = 1008, EV_BC_SCATTER = 1009;      // NoReplicationOverlap: scatter of R beside trtri
-  static constexpr int EV_LA_LEAD = 1010, EV_LA_REST = 1014, LA_STREAM0 = 2, LA_MAX_DEPTH = 2;
-  // smallest trailing block whose update is split; read per call so that tests can exercise the path at small orders.
-  // OFF by default since round 4 (CAPITAL_LOOKAHEAD=1: from order 2048; CAPITAL_LOOKAHEAD_MIN=n: from order n; CAPITAL_NO_LOOKAHEAD: off whatever else is set).
-  // Measured on one box with launches in resident rounds, alternating: n = 65536 1705.5 / 1706.0 ms with the lookahead against 1699.5 / 1700.4 without,
-  // n = 32768 237.9 / 237.9 against 236.7 / 236.6 (profiles/r4_lookahead_ab.txt).  Why it cannot pay: the chain's kernels need what a resident tile
-  // workgroup holds -- the diagonal-block kernel 132 KB of LDS, i.e. a CU with NO tile workgroup on it -- so beside a bulk launch the chain advances
-  // only when a resident round drains (one kernel per 2-4 ms), while the bulk's rounds run at 0.86-0.88 of peak beside it instead of 0.91-0.92 alone.
-  static int64_t lookahead_min() {
-    if (getenv("CAPITAL_NO_LOOKAHEAD")) return -1;
-    const char* e = getenv("CAPITAL_LOOKAHEAD_MIN");
-    if (e) return (int64_t)atoll(e);
-    return getenv("CAPITAL_LOOKAHEAD") ? (int64_t)2048 : -1;
+
+  // cholinv.hpp:93: a block of local order dim on a d x d slice splits unless its aggregate fits the base case or its leading part is shorter than the split
+  template <typename ArgType, typename U>
+  static bool splits(const ArgType& args, U dim, U d) { return !(((dim * d) <= args.bcDimension) || ((dim >> args.split) < args.split)); }
+
+  // the base-case size rule (cholinv.hpp:15-18) and the dimension fields of a factorisation of A, either mode
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void set_dimensions(const MatrixType& A, ArgType& args, CommType&& CommInfo) {
+    using U = typename ArgType::DimensionType;
+    const U localDimension = A.num_rows_local();
+    U bcDimLocal = (U)(CommInfo.c * CommInfo.d);
+    U bcMult = args.bc_mult_dim;
+    if (bcMult < 0) { bcMult = -bcMult; for (U i = 0; i < bcMult; ++i) bcDimLocal *= 2; } else { for (U i = 0; i < bcMult; ++i) bcDimLocal /= 2; }
+    bcDimLocal = std::max<U>(1, bcDimLocal);
+    bcDimLocal = std::min<U>(localDimension, bcDimLocal);
+    bcDimLocal = localDimension / bcDimLocal;
+    args.localDimension = args.trueLocalDimension = localDimension;
+    args.globalDimension = args.trueGlobalDimension = A.num_rows_global();
+    args.bcDimension = (U)CommInfo.d * bcDimLocal;
+    args.num_base_cases = args.num_levels = 0;
   }
 
-  // how many trailing updates may run beside the recursion at once (CAPITAL_LA_DEPTH, default and maximum LA_MAX_DEPTH = 2 bulk streams)
-  static int lookahead_depth() {
-    const char* e = getenv("CAPITAL_LA_DEPTH");
-    return e ? std::max(0, std::min(atoi(e), (int)LA_MAX_DEPTH)) : (int)LA_MAX_DEPTH;
+  // Registers R and, with_inverse, R^-1 for a factorisation of A, with their full-storage images when the returned structure is packed, and
+  // returns the images that the recursion works in.  No memset follows: a registered block is zero from matrix::allocate, and no
+  // factorisation ever stores a non-zero where the result must be zero (strictly-lower parts; the skipped R^-1_12 at the top level), so a block
+  // that an earlier call left registered is still zero there.
+  struct working { double *R = nullptr, *Rinv = nullptr; };
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static working working_images(const MatrixType& A, ArgType& args, CommType&& CommInfo, bool with_inverse) {
+    constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
+    auto reg = [&](auto& m) { m._register_(A.num_columns_global(), A.num_rows_global(), CommInfo.d, CommInfo.d); };
+    reg(args.R);
+    if (with_inverse) reg(args.Rinv);
+    if (packed) { reg(args.Rfull); if (with_inverse) reg(args.Rinvfull); }
+    working w;
+    w.R = packed ? args.Rfull.data() : (double*)args.R.data();
+    if (with_inverse) w.Rinv = packed ? args.Rinvfull.data() : (double*)args.Rinv.data();
+    return w;
   }
 
   // columns [x0,x1), rows [y0,y1) of a full local image into the packed (uppertri) factor; shape = what is copied per column
@@ -865,12 +849,11 @@ private:
   }
 
   template <typename ArgType, typename CommType, typename U>
-  static void invoke(ArgType& args, CommType&& t, double* R, double* Ri, U ld, U start, U localDim, U globalDim, int wait_ev = -1) {
+  static void invoke(ArgType& args, CommType&& t, double* R, double* Ri, U ld, U start, U localDim, U globalDim) {
     using matmult::view;
     capi_handle_t h = capital::handle();
     const U split1 = localDim >> args.split;
-    if (((localDim * (U)t.d) <= args.bcDimension) || (split1 < args.split)) {     // cholinv.hpp:93
-      if (wait_ev >= 0) CAPITAL_CHECK(capi_event_wait(h, wait_ev));
+    if (!splits(args, localDim, (U)t.d)) {
       CRITTER_START(CI::factor_diag);
       base_case(args, t, R, Ri, ld, start, localDim);
       CRITTER_STOP(CI::factor_diag);
@@ -888,15 +871,11 @@ private:
     view I12{Ri + start + (start + split1) * ld, ld, split1, split2};
 
     invoke(args, t, R, Ri, ld, start, split1, globalDim >> 1);                          // 1
-    // everything of this block beyond its leading part was updated by the parent on a bulk stream: join it here
-    if (wait_ev >= 0) CAPITAL_CHECK(capi_event_wait(h, wait_ev));
     if (start == 0 && args.input_lead > 0 && split1 == args.input_lead) CAPITAL_CHECK(capi_event_wait(h, EV_INPUT_MID));   // rest of the input's left half
 
     const bool top = (localDim == args.localDimension) && args.early_split == split1;
     if (top) CAPITAL_CHECK(capi_event_wait(h, EV_INPUT_REST));                          // the input's right part has landed
     CRITTER_START(CI::trsm);                                                            // 2
-    int child_wait = -1;
-    bool copy_deferred = false;
     const int64_t mark = ws.top;
     {
       view W{ws.take((int64_t)split1 * split2), split1, split1, split2};
@@ -923,53 +902,11 @@ private:
         }
         matmult::summa::trmm(t, CAPI_LEFT, CAPI_UPPER, CAPI_TRANS, CAPI_NONUNIT, 1.0, Tx, A12, W, ws);
       }
-      const U lead = split2 >> args.split;
-      const bool a22_splits = !(((split2 * (U)t.d) <= args.bcDimension) || (lead < args.split));
-      const bool la = single && a22_splits && lead > 0 && lookahead_min() >= 0 && (int64_t)split2 >= lookahead_min() && args.la_depth < lookahead_depth();
-      const bool pack_now = top && !std::is_same<typename SP::structure, rect>::value;
-      // R12 into R (cholinv.hpp:122).  At the top level with lookahead and packed factors nothing reads it there before the
-      // early packing: the copy then goes with the packing, behind the bulk of the update (W stays allocated until the join)
-      const bool copy_later = la && pack_now && !getenv("CAPITAL_PACK_AT_ONCE");
-      if (!copy_later) CAPITAL_CHECK(capi_dlacpy(h, 0, split1, split2, W.p, W.ld, A12.p, ld));
-      copy_deferred = copy_later;
+      CAPITAL_CHECK(capi_dlacpy(h, 0, split1, split2, W.p, W.ld, A12.p, ld));              // R12 into R (cholinv.hpp:122)
       CRITTER_STOP(CI::trsm);
-      // R11, R12 and Rinv11 are final after step 2: they are packed on the second stream.  Without lookahead the packing
-      // starts at once, beside the trailing update; with it, it waits for the bulk of the top-level update and then runs
-      // beside the trailing block's latency-bound chain, where the GPU is otherwise idle (beside a tile kernel the packing
-      // kernels' short workgroups keep whole CUs from the 512-thread-per-CU tile workgroups: the update lost ~10 %)
-      auto early_pack = [&](int after_ev) {
-        CAPITAL_CHECK(capi_stream_select(h, 1));
-        CAPITAL_CHECK(capi_event_wait(h, after_ev));
-        if (copy_later) CAPITAL_CHECK(capi_dlacpy(h, 0, split1, split2, W.p, W.ld, A12.p, ld));
-        pack_block(args, CAPI_UPPERTRI, R, (double*)args.R.data(), ld, (U)0, split1, (U)0, split1);
-        pack_block(args, CAPI_RECT, R, (double*)args.R.data(), ld, split1, ld, (U)0, split1);
-        pack_block(args, CAPI_UPPERTRI, Ri, (double*)args.Rinv.data(), ld, (U)0, split1, (U)0, split1);
-        CAPITAL_CHECK(capi_event_record(h, EV_EARLY_PACK));
-        CAPITAL_CHECK(capi_stream_select(h, 0));
-      };
-      bool packed_early = false;
 
       CRITTER_START(CI::tmu);                                                           // 3
-      // Lookahead: the trailing block's recursion starts with a long chain of latency-bound kernels on its leading
-      // part, which needs only that part updated.  Update it first; the rest of the update runs on a low-priority
-      // bulk stream beside that chain and is joined before the trailing block's own R12 product.
-      if (la) {
-        const int depth = args.la_depth;
-        const U rest = split2 - lead;
-        double* Wr = W.p + (int64_t)lead * W.ld;
-        CAPITAL_CHECK(capi_dgemmt(h, CAPI_UPPER, CAPI_TRANS, CAPI_NOTRANS, lead, split1, -1.0, W.p, W.ld, W.p, W.ld, 1.0, A22.p, ld));
-        CAPITAL_CHECK(capi_event_record(h, EV_LA_LEAD + depth));
-        CAPITAL_CHECK(capi_stream_select(h, LA_STREAM0 + depth));
-        CAPITAL_CHECK(capi_event_wait(h, EV_LA_LEAD + depth));
-        CAPITAL_CHECK(capi_dgemm(h, CAPI_TRANS, CAPI_NOTRANS, lead, rest, split1, -1.0, W.p, W.ld, Wr, W.ld, 1.0, A22.p + (int64_t)lead * ld, ld));
-        CAPITAL_CHECK(capi_dgemmt(h, CAPI_UPPER, CAPI_TRANS, CAPI_NOTRANS, rest, split1, -1.0, Wr, W.ld, Wr, W.ld, 1.0,
-                                  A22.p + lead + (int64_t)lead * ld, ld));
-        CAPITAL_CHECK(capi_event_record(h, EV_LA_REST + depth));
-        CAPITAL_CHECK(capi_stream_select(h, 0));
-        child_wait = EV_LA_REST + depth;
-        ++args.la_depth;                  // W stays allocated until the trailing block's recursion has joined
-        if (pack_now && !getenv("CAPITAL_PACK_AT_ONCE")) { early_pack(EV_LA_REST + depth); packed_early = true; }
-      } else if (single) {
+      if (single) {
         CAPITAL_CHECK(capi_dgemmt(h, CAPI_UPPER, CAPI_TRANS, CAPI_NOTRANS, split2, split1, -1.0, W.p, W.ld, W.p, W.ld, 1.0, A22.p, ld));
       } else {
         view Wx{ws.take(W.count()), split1, split1, split2};
@@ -977,20 +914,26 @@ private:
         util::transpose_raw(Wx.p, Wx.count(), ws.take(Wx.count()), t, matmult::summa::relay_space(t, Wx.count(), ws));
         matmult::summa::syrk(t, CAPI_UPPER, CAPI_TRANS, -1.0, W, Wx, 1.0, A22, ws);
       }
-      if (pack_now && !packed_early) {
+      // R11, R12 and Rinv11 are final after step 2: with packed factors the top level packs them on the second stream, at once, beside
+      // the trailing update and the trailing block's recursion (factor() packs the rest and joins EV_EARLY_PACK)
+      if (top && !std::is_same<typename SP::structure, rect>::value) {
         CAPITAL_CHECK(capi_event_record(h, EV_TOP_R12));
-        early_pack(EV_TOP_R12);
+        CAPITAL_CHECK(capi_stream_select(h, 1));
+        CAPITAL_CHECK(capi_event_wait(h, EV_TOP_R12));
+        pack_block(args, CAPI_UPPERTRI, R, (double*)args.R.data(), ld, (U)0, split1, (U)0, split1);
+        pack_block(args, CAPI_RECT, R, (double*)args.R.data(), ld, split1, ld, (U)0, split1);
+        pack_block(args, CAPI_UPPERTRI, Ri, (double*)args.Rinv.data(), ld, (U)0, split1, (U)0, split1);
+        CAPITAL_CHECK(capi_event_record(h, EV_EARLY_PACK));
+        CAPITAL_CHECK(capi_stream_select(h, 0));
       }
-      if (child_wait < 0) ws.top = mark;
+      ws.top = mark;
       CRITTER_STOP(CI::tmu);
     }
 
-    invoke(args, t, R, Ri, ld, start + split1, split2, split2 * (U)t.d, child_wait);    // 4
-    if (child_wait >= 0) { --args.la_depth; ws.top = mark; }
+    invoke(args, t, R, Ri, ld, start + split1, split2, split2 * (U)t.d);                // 4
 
     CRITTER_START(CI::tmu);                                                             // 5
     if (!(!args.complete_inv && (globalDim == args.trueGlobalDimension))) {
-      if (copy_deferred) CAPITAL_CHECK(capi_event_wait(h, EV_EARLY_PACK));              // R12 reached R on the second stream
       const int64_t mark = ws.top;
       view W2{ws.take((int64_t)split1 * split2), split1, split1, split2};
       matmult::summa::trmm(t, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, 1.0, R11i, A12, W2, ws);

@@ -115,7 +115,7 @@ inline void dev_copy(double* dst, const double* src, int64_t count) {
 }
 
 // Scope in which every large launch of the handle goes out one resident round at a time (capi_set_launch_rounds): for schedules whose
-// products all run on ONE stream -- grids (the lookahead is a single-GPU device), the TRSM mode.  CAPITAL_NO_LAUNCH_ROUNDS keeps the defaults.
+// products all run on ONE stream -- cholinv::factor on one GPU and on grids, the TRSM mode.  CAPITAL_NO_LAUNCH_ROUNDS keeps the defaults.
 struct launch_rounds_scope {
   int was = 0;
   bool active = false;

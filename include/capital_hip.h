@@ -412,10 +412,10 @@ int capi_gather(capi_comm_t c, const double* send, double* recv, int64_t count_p
 int capi_scatter(capi_comm_t c, const double* send, double* recv, int64_t count_per_rank, int root);  /* MPI_Scatter / MPI_Iscatter, policy.h:361-377,470-488 */
 
 /* ---- extra streams + events: lets the host layer run collectives beside the tile kernel (the reference's
- *      MPI_Ibcast/Iallreduce chunk pipeline, summa.hpp:195-215,238-249) and the bulk of a trailing update beside the
- *      next block's factorisation.  capi_stream_select(h, i) routes every following call on this handle (kernels,
- *      copies, collectives) to stream i: 0 = compute stream, 1 = communication / packing stream, 2..3 = low-priority bulk
- *      streams.  Each stream index has its own private workspace; events order work across streams (slot in [0, 1024)). ---- */
+ *      MPI_Ibcast/Iallreduce chunk pipeline, summa.hpp:195-215,238-249) and copies or packing beside a factorisation.
+ *      capi_stream_select(h, i) routes every following call on this handle (kernels, copies, collectives) to stream i:
+ *      0 = compute stream, 1 = communication / packing stream; any other index is CAPI_EINVAL.  Each stream index has its
+ *      own private workspace; events order work across streams (slot in [0, 1024)). ---- */
 int capi_stream_select(capi_handle_t h, int which);
 int capi_event_record(capi_handle_t h, int slot);   /* on the currently selected stream */
 int capi_event_wait(capi_handle_t h, int slot);     /* the currently selected stream waits for that record */

@@ -208,6 +208,23 @@ def test_two_streams_and_events(hip, oracle):
     assert float(y[0]) == 14.0 and float(y[-1]) == 14.0 and float(z[12345]) == 7.0
 
 
+def test_stream_select_takes_two_indices(hip):
+    """capi_stream_select: 0 (compute) and 1 (communication / packing) are the handle's streams; any other index is CAPI_EINVAL,
+    names the argument, and leaves the selected stream as it was: a product launched afterwards is right"""
+    from capital_amd import capi
+    hip.call("capi_stream_select", 1)
+    hip.call("capi_stream_select", 0)
+    for bad in (2, -1):
+        assert hip.L.capi_stream_select(hip.h, bad) == -1                    # CAPI_EINVAL
+        assert "stream index" in hip.L.capi_last_error(hip.h).decode()
+    n = 128
+    A = np.asfortranarray(np.eye(n))
+    B = np.asfortranarray(np.arange(n * n, dtype=np.float64).reshape(n, n) % 97 + np.arange(n)[:, None] * 0.5)
+    dA, dB, dC = capi.to_device(A), capi.to_device(B), capi.zeros(n, n)
+    hip.call("capi_dgemm", 0, 0, n, n, n, 1.0, capi.ptr(dA), n, capi.ptr(dB), n, 0.0, capi.ptr(dC), n)
+    np.testing.assert_array_equal(capi.to_host(dC), B)
+
+
 @pytest.mark.parametrize("rl,d", [(8, 2), (5, 3), (16, 1), (33, 2)])
 def test_block_cyclic_triangle(hip, oracle, rl, d):
     """packed-triangle pieces (util.hpp:57-102,167-201): device kernels bit-exact against the oracle's restatement, and a round
