@@ -3,6 +3,7 @@
 //
 //   capi_dberr        berr[j] <- max_i |rho_ij| / w_ij (dporfs's guarded quotient), W <- |rho| + (n + 1) eps W: the weights of the forward bound
 //   capi_dcolamax     colmax[j] <- max_i |X(i, j)|
+//   capi_dcolnorm2    out[j] <- sum_i X(i, j)^2 (cholinv::quadratic_forms: b^T A^-1 b from R^-T b)
 //   capi_dlacn_block  one transition of the Hager-Higham 1-norm estimator (dlacn2) for r columns in lockstep, by reverse communication
 //
 // One workgroup of 256 threads per column.  A thread takes the lines tid, tid + 256, ..; its partial results meet in a butterfly inside the wave and
@@ -79,6 +80,15 @@ __global__ __launch_bounds__(BD_THREADS) void colamax_kernel(int64_t n, const do
   for (int64_t i = threadIdx.x; i < n; i += BD_THREADS) s = tt::max_nan(s, fabs(x[i]));
   s = block_max(s, red);
   if (threadIdx.x == 0) colmax[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(BD_THREADS) void colnorm2_kernel(int64_t n, const double* __restrict__ X, int64_t ldx, double* __restrict__ out) {
+  __shared__ double red[4];
+  const double* x = X + (int64_t)blockIdx.x * ldx;
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += BD_THREADS) s += x[i] * x[i];
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
 // ---- the estimator.  Per column the state is LACN_HEAD doubles and the n signs of dlacn2's ISGN; behind the r columns lie the words of the count ----
@@ -229,6 +239,15 @@ int capi_dcolamax(capi_handle_t h, int64_t n, int64_t r, const double* X, int64_
   CAPI_REQUIRE_THIN_R(h, r);
   CAPI_REQUIRE(h, n >= 0 && colmax && (n == 0 || (X && ldx >= n)), "n/X/ldx/colmax");
   hipLaunchKernelGGL(colamax_kernel, dim3((unsigned)r), dim3(BD_THREADS), 0, h->stream, n, X, ldx, colmax);
+  CAPI_HIP_CHECK(h, hipGetLastError());
+  return CAPI_OK;
+}
+
+int capi_dcolnorm2(capi_handle_t h, int64_t n, int64_t r, const double* X, int64_t ldx, double* out) {
+  CAPI_REQUIRE(h, h, "null handle");
+  CAPI_REQUIRE_THIN_R(h, r);
+  CAPI_REQUIRE(h, n >= 0 && out && (n == 0 || (X && ldx >= n)), "n/X/ldx/out");
+  hipLaunchKernelGGL(colnorm2_kernel, dim3((unsigned)r), dim3(BD_THREADS), 0, h->stream, n, X, ldx, out);
   CAPI_HIP_CHECK(h, hipGetLastError());
   return CAPI_OK;
 }

@@ -63,6 +63,10 @@ def bind(D):
     D.capital_cholinv_update.argtypes = [_vp, _i64, _dp, _int]
     D.capital_cholinv_factor_pivoted.argtypes = [_vp, _dbl, _i64, C.POINTER(_i64), _dp, _dp]
     D.capital_cholinv_get_pivoted.argtypes = [_vp, _dp, C.POINTER(_int), _dp]
+    D.capital_cholinv_apply.argtypes = [_vp, _int, _i64, _dp, _dp]
+    D.capital_cholinv_quadratic_forms.argtypes = [_vp, _i64, _dp, _dp]
+    D.capital_cholinv_logdet.argtypes = [_vp, _dp]
+    D.capital_cholinv_inverse_diagonal.argtypes = [_vp, _dp]
     D.capital_cacqr_create.argtypes = [_i64, _i64] + [_int] * 8
     D.capital_cacqr_create.restype = _vp
     D.capital_cacqr_set_A.argtypes = [_vp, _dp]
@@ -241,6 +245,50 @@ class Cholinv:
         if v.ndim != 2 or v.shape[0] != self.n or v.shape[1] < 1:
             raise DriverError(f"Cholinv.update: V must be {self.n} x r with r >= 1, got {v.shape}")
         _ck(self.D.capital_cholinv_update(self.p, v.shape[1], v.ctypes.data_as(_dp), -1 if downdate else 1), "update")
+
+    def _thin_block(self, B, who):
+        b = np.asfortranarray(B, dtype=np.float64)
+        if b.ndim == 1:
+            b = np.asfortranarray(b[:, None])
+        if b.ndim != 2 or b.shape[0] != self.n or b.shape[1] < 1:
+            raise DriverError(f"Cholinv.{who}: B must be {self.n} x r with r >= 1, got {b.shape}")
+        return b
+
+    _FACTOR_OPS = {"R": 0, "RT": 1, "Rinv": 2, "RinvT": 3}
+
+    def apply(self, B, op):
+        """op B for one of the four triangular operators of A = R^T R, on the factors of the last factor() or update() (cholesky::cholinv::apply, one
+        rank): op = "R", "RT" (R^T z samples N(0, A)), "Rinv" (R^-1 z samples N(0, A^-1)) or "RinvT" (R^-T b whitens b).  B: n x r, any r >= 1.
+        "R" and "RT" are one thin product with R as it lies, in every mode; the inverses are one half of solve()'s operator in the form the flags
+        select, so apply(apply(B, "RinvT"), "Rinv") is solve(B, refine=0)[0] bit for bit.  The X of the last solve stays as it is.  Returns n x r."""
+        if op not in self._FACTOR_OPS:
+            raise DriverError(f"Cholinv.apply: op must be one of {sorted(self._FACTOR_OPS)}, got {op!r}")
+        b = self._thin_block(B, "apply")
+        Y = np.zeros(b.shape, order="F")
+        _ck(self.D.capital_cholinv_apply(self.p, self._FACTOR_OPS[op], b.shape[1], b.ctypes.data_as(_dp), Y.ctypes.data_as(_dp)), "apply")
+        return Y
+
+    def quadratic_forms(self, B):
+        """q[j] = b_j^T A^-1 b_j = ||R^-T b_j||^2, the squared Mahalanobis lengths of B's columns (cholesky::cholinv::quadratic_forms, one rank): half
+        a solve and a column norm; the half-solve is not kept.  B: n x r.  Returns r values."""
+        b = self._thin_block(B, "quadratic_forms")
+        q = np.zeros(b.shape[1])
+        _ck(self.D.capital_cholinv_quadratic_forms(self.p, b.shape[1], b.ctypes.data_as(_dp), q.ctypes.data_as(_dp)), "quadratic_forms")
+        return q
+
+    def logdet(self):
+        """log det A = 2 sum_i log r_ii from the resident R (cholesky::cholinv::log_determinant, one rank), in every mode"""
+        v = _dbl()
+        _ck(self.D.capital_cholinv_logdet(self.p, C.byref(v)), "logdet")
+        return v.value
+
+    def inverse_diagonal(self):
+        """diag(A^-1): the sums of squares of the rows of the resident R^-1 (cholesky::cholinv::inverse_diagonal, one rank), one pass over the
+        triangle.  With complete_inv=0 and a split top level the block R^-1_12 that factor() skipped is formed for the call (its two triangular
+        products and n^2 / 4 doubles of work) and released.  Raises DriverError in TRSM mode, which has no inverse.  Returns n values."""
+        d = np.zeros(self.n)
+        _ck(self.D.capital_cholinv_inverse_diagonal(self.p, d.ctypes.data_as(_dp)), "inverse_diagonal")
+        return d
 
     def factor_pivoted(self, rtol=0.0, max_rank=None):
         """A ~= L L^T with L n x rank by a diagonally pivoted, partial Cholesky (cholesky::cholinv::factor_pivoted, one rank): for a symmetric matrix

@@ -51,6 +51,10 @@ struct cholinv_problem {
   virtual void update(int64_t r, const double* V_host, int sign) = 0;
   virtual void factor_pivoted(double rtol, int64_t max_rank, int64_t* rank, double* resid_trace, double* thresh) = 0;
   virtual void get_pivoted(double* L_host, int* piv_host, double* d_host) = 0;
+  virtual void apply(int op, int64_t r, const double* B_host, double* Y_host) = 0;
+  virtual void quadratic_forms(int64_t r, const double* B_host, double* q_host) = 0;
+  virtual void logdet(double* v) = 0;
+  virtual void inverse_diagonal(double* d_host) = 0;
 };
 
 template <class Alg>
@@ -139,6 +143,33 @@ struct cholinv_impl : cholinv_problem {
     if (L_host) CAPITAL_CHECK(capi_memcpy_d2h(capital::handle(), L_host, pack.Lp.data(), sizeof(double) * (size_t)(n * pack.pivot_rank)));
     if (piv_host) std::memcpy(piv_host, pack.pivl.data(), sizeof(int) * (size_t)n);
     if (d_host) fetch(pack.Dres, d_host);
+  }
+  // Y = op B on the factors of the last factor(): op 0 R, 1 R^T, 2 R^-1, 3 R^-T; B_host n x r column-major, Y_host receives n x r
+  void apply(int op, int64_t r, const double* B_host, double* Y_host) override {
+    if (op < 0 || op > 3 || r < 1 || !B_host || !Y_host) throw std::invalid_argument("cholinv apply: op 0..3 (R, RT, Rinv, RinvT), r >= 1 columns, B and Y expected");
+    static const cholesky::factor_op ops[4] = {cholesky::factor_op::R, cholesky::factor_op::Rt, cholesky::factor_op::Rinv, cholesky::factor_op::RinvT};
+    MatrixType B(r, A.num_rows_global(), 1, 1);
+    B.from_host(B_host);
+    Alg::apply(B, pack, grid, ops[op]);
+    fetch(pack.Y, Y_host);
+  }
+  // q_host[j] = b_j^T A^-1 b_j
+  void quadratic_forms(int64_t r, const double* B_host, double* q_host) override {
+    if (r < 1 || !B_host || !q_host) throw std::invalid_argument("cholinv quadratic_forms: r >= 1 columns, B and a place for the r results expected");
+    MatrixType B(r, A.num_rows_global(), 1, 1);
+    B.from_host(B_host);
+    Alg::quadratic_forms(B, pack, grid);
+    std::memcpy(q_host, pack.quad.data(), sizeof(double) * (size_t)r);
+  }
+  void logdet(double* v) override {
+    if (!v) throw std::invalid_argument("cholinv logdet: a place for the result expected");
+    Alg::log_determinant(pack, grid);
+    *v = pack.logdet;
+  }
+  void inverse_diagonal(double* d_host) override {
+    if (!d_host) throw std::invalid_argument("cholinv inverse_diagonal: a place for the n results expected");
+    Alg::inverse_diagonal(pack, grid);
+    std::memcpy(d_host, pack.inv_diag.data(), sizeof(double) * pack.inv_diag.size());
   }
 };
 
@@ -371,6 +402,20 @@ int capital_cholinv_factor_pivoted(void* p, double rtol, int64_t max_rank, int64
 int capital_cholinv_get_pivoted(void* p, double* L_host /* n x rank */, int* piv_host /* n */, double* d_host /* n */) {
   return guarded([&] { ((cholinv_problem*)p)->get_pivoted(L_host, piv_host, d_host); });
 }
+// The factors themselves (cholesky::cholinv::apply / quadratic_forms / log_determinant / inverse_diagonal; one rank, after capital_cholinv_factor, also
+// after capital_cholinv_update).  capital_cholinv_apply: Y_host (n x r) <- op B_host, op = 0 R, 1 R^T, 2 R^-1, 3 R^-T (A = R^T R); the X of the last
+// solve stays as it is
+int capital_cholinv_apply(void* p, int op, int64_t r, const double* B_host, double* Y_host) {
+  return guarded([&] { ((cholinv_problem*)p)->apply(op, r, B_host, Y_host); });
+}
+// q_host[j] <- b_j^T A^-1 b_j, r results
+int capital_cholinv_quadratic_forms(void* p, int64_t r, const double* B_host, double* q_host) {
+  return guarded([&] { ((cholinv_problem*)p)->quadratic_forms(r, B_host, q_host); });
+}
+// *v <- log det A
+int capital_cholinv_logdet(void* p, double* v) { return guarded([&] { ((cholinv_problem*)p)->logdet(v); }); }
+// d_host[i] <- (A^-1)_ii, n results; -1 in TRSM mode, which has no inverse
+int capital_cholinv_inverse_diagonal(void* p, double* d_host) { return guarded([&] { ((cholinv_problem*)p)->inverse_diagonal(d_host); }); }
 int capital_cholinv_destroy(void* p) { return guarded([&] { capital::sync(); delete (cholinv_problem*)p; }); }
 
 void* capital_cacqr_create(int64_t m, int64_t n, int c, int variant, int layout, int num_chunks, int complete_inv, int split, int bc_mult, int serialize_) {

@@ -40,8 +40,16 @@
 // .. and the pivoted partial factorization: without them factor_pivoted() refuses and everything else runs as before
 #pragma weak capi_dpchol
 #pragma weak capi_dpchol_thresh
+// .. and the reductions over the factors themselves: without them quadratic_forms(), log_determinant() and inverse_diagonal() refuse (apply() needs
+// none of them) and everything else runs as before
+#pragma weak capi_dtri_rownorm2
+#pragma weak capi_dtri_logdiag
+#pragma weak capi_dcolnorm2
 
 namespace cholesky {
+
+// which of the four triangular operators of the factorisation A = R^T R cholinv::apply applies to a block
+enum class factor_op { R, Rt, Rinv, RinvT };
 
 template <class SerializePolicy = policy::cholinv::Serialize, class IntermediatesPolicy = policy::cholinv::SaveIntermediates,
           class BaseCasePolicy = policy::cholinv::NoReplication>
@@ -109,6 +117,12 @@ public:
     matmult::arena ops;
     // update(): the step of the last failed downdate (0: none)
     int update_info = 0;
+    // The factors themselves.  apply(): Y (n x r) = op B for one of R, R^T, R^-1, R^-T; quadratic_forms(): quad[j] = b_j^T A^-1 b_j (Quad: its device
+    // image); log_determinant(): logdet = log det A; inverse_diagonal(): inv_diag[i] = (A^-1)_ii, InvDiag its device image (n doubles).  None of
+    // these is read by factor(), solve(), condition(), error_bounds() or update(), and X is not written by any of the four.
+    matrix<ScalarType, DimensionType, rect> Y, Quad, InvDiag;
+    std::vector<double> quad, inv_diag;
+    double logdet = 0.0;
     // factor_pivoted().  Input: pivot_rtol -- the factorization stops where the largest remaining Schur diagonal entry is <= pivot_rtol trace(A); 0:
     // LAPACK dpstrf's default n u max_i a_ii; pivot_max_rank -- the most columns of L, 0: min(n, CAPI_PCHOL_MAX_RANK).  Results: Lp (n x max_rank, the
     // first pivot_rank columns valid, in A's own row ordering), pivl (host) / PivL (device: n ints in the first (n + 1) / 2 doubles): the chosen rows in
@@ -443,6 +457,167 @@ public:
                               "); A is unchanged, R and Rinv are not valid: factor() again");
   }
 
+  // ---- the factors themselves: A = R^T R for whitening (R^-T b), sampling (R^T z ~ N(0, A), R^-1 z ~ N(0, A^-1)), the Gaussian log-likelihood
+  // (b^T A^-1 b, log det A) and leave-one-out quantities (diag A^-1).  ONE rank, solve()'s preconditions (require_factors); O(n^2 r) or less on what is
+  // resident; no n x n inverse is formed or stored.  After update() they work on the updated factors; after a failed downdate they refuse. ----
+
+  // args.Y (n x r) <- op B, op one of R, R^T, R^-1, R^-T.  B: matrix<double, int64_t, rect>(r, n, 1, 1), any r >= 1, CAPI_TS_MAX_RHS columns at a time; B
+  // and args.X are not written (error_bounds() after an apply() still sees the X of the last solve()).
+  //   R, Rt        one capi_dtrmm_thin(CAPI_UPPERTRI) on R as it lies, packed or rect: in every mode, TRSM mode included
+  //   Rinv, RinvT  one half of solve()'s operator (apply_half) in the form the flags select: substitution on R, capi_dtrsm on the full-storage R (TRSM
+  //                mode), one product with the complete R^-1, or the block form; apply(Rinv, apply(RinvT, B)) is solve(B, refine = 0) bit for bit
+  // Memory, of args.ops: one n x CAPI_TS_MAX_RHS block for the inverses in the block form, none otherwise.
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void apply(const MatrixType& B, ArgType& args, CommType&& CommInfo, factor_op op) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::apply takes a rect-structured B");
+    require_factors(args, CommInfo, "cholinv::apply");
+    const int64_t n = args.localDimension, r = B.num_columns_global();
+    if (r < 1 || B.num_rows_global() != n || B.num_rows_local() != n)
+      throw std::invalid_argument("cholinv::apply: B must be n x r with r >= 1 (matrix(r, n, 1, 1))");
+    const bool inverse = op == factor_op::Rinv || op == factor_op::RinvT;
+    const int trans = (op == factor_op::Rt || op == factor_op::RinvT) ? CAPI_TRANS : CAPI_NOTRANS;
+    // (R and R^T need the thin image of R alone: they run where a form of solve() has no image to run on)
+    applier ap{};
+    if (inverse) ap = make_applier(args, "cholinv::apply");
+    const image Rw = pick_image(args.R, args.Rfull, n, image_use::thin_read, "cholinv::apply");
+    CRITTER_START(CI::apply);
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    const int64_t W = CAPI_TS_MAX_RHS;
+    util::resize_columns(args.Y, r, n);
+    ops_scope ops(args.ops, inverse ? half_work_blocks(ap) : 0, n, 0);
+    if (inverse) take_half_work(ap, ops);
+    const typename image::block T = Rw.at(0, 0);
+    for (int64_t j = 0; j < r && n > 0; j += W) {
+      const int64_t rb = std::min(W, r - j);
+      if (inverse) apply_half(ap, trans, B.data() + j * n, args.Y.data() + j * n, rb);
+      else CAPITAL_CHECK(capi_dtrmm_thin(h, CAPI_UPPERTRI, trans, n, n, rb, 1.0, T.p, T.ldt, T.col0, B.data() + j * n, n, 0.0, args.Y.data() + j * n, n));
+    }
+    CRITTER_STOP(CI::apply);
+  }
+
+  // args.quad[j] = b_j^T A^-1 b_j = ||R^-T b_j||^2 (the squared Mahalanobis length of b_j; args.Quad is its device image).  B as in apply().  Per block
+  // of CAPI_TS_MAX_RHS columns: apply_half(R^-T) into a work block, then capi_dcolnorm2; the half-solve is not kept, B, args.X and args.Y are not written.
+  // Memory, of args.ops: one n x CAPI_TS_MAX_RHS block, two in the block form.
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void quadratic_forms(const MatrixType& B, ArgType& args, CommType&& CommInfo) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::quadratic_forms takes a rect-structured B");
+    require_factors(args, CommInfo, "cholinv::quadratic_forms");
+    if (!&capi_dcolnorm2) throw std::logic_error("cholinv: this C-ABI library has no capi_dcolnorm2: no quadratic forms");
+    const int64_t n = args.localDimension, r = B.num_columns_global();
+    if (r < 1 || B.num_rows_global() != n || B.num_rows_local() != n)
+      throw std::invalid_argument("cholinv::quadratic_forms: B must be n x r with r >= 1 (matrix(r, n, 1, 1))");
+    applier ap = make_applier(args, "cholinv::quadratic_forms");
+    CRITTER_START(CI::quadratic_forms);
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    const int64_t W = CAPI_TS_MAX_RHS;
+    util::resize_columns(args.Quad, r, 1);
+    {
+      ops_scope ops(args.ops, half_work_blocks(ap) + 1, n, 0);
+      take_half_work(ap, ops);
+      double* const y = ops.block();
+      for (int64_t j = 0; j < r; j += W) {
+        const int64_t rb = std::min(W, r - j);
+        if (n > 0) apply_half(ap, CAPI_TRANS, B.data() + j * n, y, rb);
+        CAPITAL_CHECK(capi_dcolnorm2(h, n, rb, y, std::max<int64_t>(n, 1), args.Quad.data() + j));
+      }
+      args.quad = args.Quad.to_host();
+    }
+    CRITTER_STOP(CI::quadratic_forms);
+  }
+
+  // args.logdet = log det A = 2 sum_i log r_ii: capi_dtri_logdiag on R as it lies, packed or rect; in every mode.  Memory, of args.ops: two doubles.
+  template <typename ArgType, typename CommType>
+  static void log_determinant(ArgType& args, CommType&& CommInfo) {
+    require_factors(args, CommInfo, "cholinv::log_determinant");
+    if (!&capi_dtri_logdiag) throw std::logic_error("cholinv: this C-ABI library has no capi_dtri_logdiag: no log-determinant");
+    const int64_t n = args.localDimension;
+    const image Rw = pick_image(args.R, args.Rfull, n, image_use::thin_read, "cholinv::log_determinant");
+    CRITTER_START(CI::log_determinant);
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    double half = 0.0;
+    {
+      ops_scope ops(args.ops, 0, n, 2);
+      double* const out = ops.piece(2);
+      const typename image::block T = Rw.at(0, 0);
+      CAPITAL_CHECK(capi_dtri_logdiag(h, n, T.p, T.ldt, T.col0, out));
+      CAPITAL_CHECK(capi_memcpy_d2h(h, &half, out, sizeof(double)));
+    }
+    args.logdet = 2.0 * half;
+    CRITTER_STOP(CI::log_determinant);
+  }
+
+  // args.inv_diag[i] (host; args.InvDiag: device, n doubles) = (A^-1)_ii = the sum of squares of row i of R^-1 (leave-one-out residuals, predictive
+  // variances).  capi_dtri_rownorm2 reads R^-1 once, as it lies, packed or rect:
+  //   complete inverse (complete_inv != 0, or the top level did not split): one pass over the triangle, no extra memory
+  //   complete_inv == 0 and the top level split at h1: the two diagonal blocks are reduced as sub-triangles, and the block that factor() never formed,
+  //       R^-1_12 = -R11^-1 R12 R22^-1 (h1 x h2; its step 5), is formed in args.ops by two triangular products on the tile kernels, added into the
+  //       leading h1 entries (CAPI_RECT, beta = 1) and released.  This form costs the skipped products, h1 h2 n flops, each time it is called -- a
+  //       caller who wants the diagonal more than once factors with complete_inv = 1 -- and h1 h2 doubles of args.ops, n^2 / 4 at an even split.
+  //       With Serialize + FlushIntermediates only packed factors are resident: R11^-1, R12 and R22^-1 are first unpacked into args.ops
+  //       (capi_serialize), h1^2 + h1 h2 + h2^2 doubles more.
+  //   TRSM mode: there is no inverse; std::logic_error.
+  // info::solve_by_substitution plays no part: the inverse is resident either way.
+  template <typename ArgType, typename CommType>
+  static void inverse_diagonal(ArgType& args, CommType&& CommInfo) {
+    require_factors(args, CommInfo, "cholinv::inverse_diagonal");
+    if (args.solve_with_trsm)
+      throw std::logic_error("cholinv::inverse_diagonal: the TRSM mode forms no inverse (info::solve_with_trsm): factor in inverse mode for diag(A^-1)");
+    if (!&capi_dtri_rownorm2) throw std::logic_error("cholinv: this C-ABI library has no capi_dtri_rownorm2: no diagonal of the inverse");
+    const int64_t n = args.localDimension, h1 = args.top_split, h2 = n - h1;
+    const bool blocks = !args.complete_inv && h1 > 0 && h1 < n;
+    constexpr bool packed = !std::is_same<typename SP::structure, rect>::value;
+    const char* const who = "cholinv::inverse_diagonal";
+    const image Ip = pick_image(args.Rinv, args.Rinvfull, n, image_use::thin_read, who);
+    args.inv_diag.clear();
+    CRITTER_START(CI::inverse_diagonal);
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    args.InvDiag._register_(1, std::max<int64_t>(n, 1), 1, 1);
+    double* const out = args.InvDiag.data();
+    auto rownorm2 = [&](int shape, int64_t m, int64_t k, const typename image::block& T, double beta, double* o) {
+      CAPITAL_CHECK(capi_dtri_rownorm2(h, shape, m, k, T.p, T.ldt, T.col0, beta, o));
+    };
+    if (!blocks) {
+      rownorm2(CAPI_UPPERTRI, n, n, Ip.at(0, 0), 0.0, out);
+    } else {
+      rownorm2(CAPI_UPPERTRI, h1, h1, Ip.at(0, 0), 0.0, out);
+      rownorm2(CAPI_UPPERTRI, h2, h2, Ip.at(h1, h1), 0.0, out + h1);
+      // the operands of the two products in column-major storage: the working images, the rect structure, or copies unpacked from the packed factors
+      const bool have_full = !packed || (IP::keep_arena && args.Rfull.filled() && args.Rinvfull.filled());
+      const int64_t c12 = even(h1 * h2), c11 = even(h1 * h1), c22 = even(h2 * h2);
+      ops_scope ops(args.ops, 0, n, c12 + (have_full ? 0 : c11 + c12 + c22));
+      double* const I12 = ops.piece(h1 * h2);
+      const double *I11, *R12, *I22;
+      int64_t ld11, ld12, ld22;
+      if (have_full) {
+        const double* const Rf = packed ? args.Rfull.data() : (const double*)args.R.data();
+        const double* const If = packed ? args.Rinvfull.data() : (const double*)args.Rinv.data();
+        I11 = If; R12 = Rf + h1 * n; I22 = If + h1 + h1 * n;
+        ld11 = ld12 = ld22 = n;
+      } else {
+        double *const u11 = ops.piece(h1 * h1), *const u12 = ops.piece(h1 * h2), *const u22 = ops.piece(h2 * h2);
+        auto unpack = [&](int shape, const double* src, double* dst, int64_t dx, int64_t dy, int64_t x0, int64_t x1, int64_t y0, int64_t y1) {
+          CAPITAL_CHECK(capi_serialize_shape(h, shape, CAPI_UPPERTRI, CAPI_RECT, src, n, n, dst, dx, dy, x0, x1, y0, y1, 0, x1 - x0, 0, y1 - y0));
+        };
+        // (the products read the upper triangles of u11 and u22 alone: what the arena holds below their diagonals is never used)
+        unpack(CAPI_UPPERTRI, (const double*)args.Rinv.data(), u11, h1, h1, 0, h1, 0, h1);
+        unpack(CAPI_RECT, (const double*)args.R.data(), u12, h2, h1, h1, n, 0, h1);
+        unpack(CAPI_UPPERTRI, (const double*)args.Rinv.data(), u22, h2, h2, h1, n, h1, n);
+        I11 = u11; R12 = u12; I22 = u22;
+        ld11 = h1; ld12 = h1; ld22 = h2;
+      }
+      CAPITAL_CHECK(capi_dtrmm_oop(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, h1, h2, 1.0, I11, ld11, R12, ld12, I12, h1));
+      CAPITAL_CHECK(capi_dtrmm(h, CAPI_RIGHT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, h1, h2, -1.0, I22, ld22, I12, h1));
+      rownorm2(CAPI_RECT, h1, h2, typename image::block{I12, h1, 0}, 1.0, out);
+    }
+    args.inv_diag.resize((size_t)n);
+    if (n > 0) CAPITAL_CHECK(capi_memcpy_d2h(h, args.inv_diag.data(), out, sizeof(double) * (size_t)n));
+    CRITTER_STOP(CI::inverse_diagonal);
+  }
+
   // A ~= Lp Lp^T by a diagonally pivoted, PARTIAL Cholesky (capi_dpchol), for a symmetric A that is only positive SEMIdefinite or numerically low-rank --
   // where factor() throws on the first non-positive pivot -- or of which k << n columns are wanted: O(n k^2), not O(n^3).  ONE rank.  Swap-free: Lp
   // (n x max_rank) is in A's own row ordering, column j belongs to the row args.pivl[j]; rows chosen before step j are exactly zero in column j.  It stops
@@ -715,8 +890,27 @@ private:
     if (c.work_blocks > 0) c.w1 = ops.block();
     if (c.work_blocks > 1) c.w2 = ops.block();
   }
-  // Xo (n x rb, ld n) <- A^-1 Bi; Bi is not written and Xo != Bi
+  // the work of ONE half (apply_half) on a caller's block: the block form builds its right-hand side in w2; w1 belongs to apply_inverse
+  static int half_work_blocks(const applier& c) { return c.blocks ? 1 : 0; }
+  static void take_half_work(applier& c, ops_scope& ops) {
+    if (c.blocks) c.w2 = ops.block();
+  }
+  // Xo (n x rb, ld n) <- A^-1 Bi; Bi is not written and Xo != Bi.  The two halves of apply_half, R^-T first: by substitution and in TRSM mode the
+  // second runs in place on Xo, by products it reads the first half's result from the work block w1
   static void apply_inverse(const applier& c, const double* Bi, double* Xo, int64_t rb) {
+    double* const y = (c.subst || c.trsm) ? Xo : c.w1;
+    apply_half(c, CAPI_TRANS, Bi, y, rb);
+    apply_half(c, CAPI_NOTRANS, y, Xo, rb);
+  }
+  // Xo (n x rb, ld n) <- R^-T Bi (trans == CAPI_TRANS) or R^-1 Bi (CAPI_NOTRANS): one half of the operator A^-1 = R^-1 R^-T, in the form the flags select.
+  //   substitution / TRSM mode   Bi is copied to Xo, which is solved in place (Bi == Xo: no copy); no work block
+  //   complete inverse           one product with R^-1, Xo != Bi; no work block
+  //   block form (complete_inv == 0 and a top split at h1), Xo != Bi:
+  //       R^-T:  y1 = R11^-T b1, y2 = R22^-T (b2 - R12^T y1)      b2 - R12^T y1 is built in the work block w2
+  //       R^-1:  x2 = R22^-1 y2, x1 = R11^-1 (y1 - R12 x2)        y1 - R12 x2 is built in w2, on a copy of y1 -- or, where Bi is the work block w1
+  //                                                               (apply_inverse's second half), in w1's own leading rows, which are then spent
+  // A caller's Bi is never written.
+  static void apply_half(const applier& c, int trans, const double* Bi, double* Xo, int64_t rb) {
     capi_handle_t h = c.h;
     const int64_t n = c.n, h1 = c.h1;
     const image &Rp = c.R, &Ip = c.Rinv;
@@ -727,29 +921,27 @@ private:
     };
     if (c.subst) {
       const typename image::block T = Rp.at(0, 0);
-      CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));
-      CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_TRANS, n, rb, T.p, T.ldt, T.col0, Xo, n));                // y = R^-T b
-      CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_NOTRANS, n, rb, T.p, T.ldt, T.col0, Xo, n));              // x = R^-1 y
-      return;
-    }
-    double* w1 = c.w1;
-    if (c.trsm) {
-      CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));
-      CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_TRANS, CAPI_NONUNIT, n, rb, 1.0, c.Rfull.p, c.Rfull.ld, Xo, n));
-      CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, n, rb, 1.0, c.Rfull.p, c.Rfull.ld, Xo, n));
+      if (Bi != Xo) CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));
+      CAPITAL_CHECK(capi_dtrsm_thin(h, trans, n, rb, T.p, T.ldt, T.col0, Xo, n));
+    } else if (c.trsm) {
+      if (Bi != Xo) CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Bi, n, Xo, n));
+      CAPITAL_CHECK(capi_dtrsm(h, CAPI_LEFT, CAPI_UPPER, trans, CAPI_NONUNIT, n, rb, 1.0, c.Rfull.p, c.Rfull.ld, Xo, n));
     } else if (!c.blocks) {
-      thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, 0, 0, n, n, rb, 1.0, Bi, 0.0, w1);
-      thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, 0, 0, n, n, rb, 1.0, w1, 0.0, Xo);
-    } else {
+      thin(Ip, CAPI_UPPERTRI, trans, 0, 0, n, n, rb, 1.0, Bi, 0.0, Xo);
+    } else if (trans == CAPI_TRANS) {
       const int64_t h2 = n - h1;
       double* w2 = c.w2;
-      thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, 0, 0, h1, h1, rb, 1.0, Bi, 0.0, w1);                          // y1 = R11^-T b1
+      thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, 0, 0, h1, h1, rb, 1.0, Bi, 0.0, Xo);                          // y1 = R11^-T b1
       CAPITAL_CHECK(capi_dlacpy(h, 0, h2, rb, Bi + h1, n, w2 + h1, n));
-      thin(Rp, CAPI_RECT, CAPI_TRANS, 0, h1, h1, h2, rb, -1.0, w1, 1.0, w2 + h1);                      // b2 - R12^T y1
-      thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, h1, h1, h2, h2, rb, 1.0, w2 + h1, 0.0, w1 + h1);             // y2 = R22^-T (..)
-      thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, h1, h1, h2, h2, rb, 1.0, w1 + h1, 0.0, Xo + h1);           // x2 = R22^-1 y2
-      thin(Rp, CAPI_RECT, CAPI_NOTRANS, 0, h1, h1, h2, rb, -1.0, Xo + h1, 1.0, w1);                    // y1 - R12 x2
-      thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, 0, 0, h1, h1, rb, 1.0, w1, 0.0, Xo);                       // x1 = R11^-1 (..)
+      thin(Rp, CAPI_RECT, CAPI_TRANS, 0, h1, h1, h2, rb, -1.0, Xo, 1.0, w2 + h1);                      // b2 - R12^T y1
+      thin(Ip, CAPI_UPPERTRI, CAPI_TRANS, h1, h1, h2, h2, rb, 1.0, w2 + h1, 0.0, Xo + h1);             // y2 = R22^-T (..)
+    } else {
+      const int64_t h2 = n - h1;
+      double* t = c.w1;
+      if (Bi != c.w1) { t = c.w2; CAPITAL_CHECK(capi_dlacpy(h, 0, h1, rb, Bi, n, t, n)); }
+      thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, h1, h1, h2, h2, rb, 1.0, Bi + h1, 0.0, Xo + h1);           // x2 = R22^-1 y2
+      thin(Rp, CAPI_RECT, CAPI_NOTRANS, 0, h1, h1, h2, rb, -1.0, Xo + h1, 1.0, t);                     // y1 - R12 x2
+      thin(Ip, CAPI_UPPERTRI, CAPI_NOTRANS, 0, 0, h1, h1, rb, 1.0, t, 0.0, Xo);                        // x1 = R11^-1 (..)
     }
   }
   // the preconditions of everything that uses the factors; `who` opens the message

@@ -236,6 +236,26 @@ int capi_dberr(capi_handle_t h, int64_t n, int64_t r, const double* Rho, int64_t
 /* capi_dcolamax: colmax[j] (DEVICE, r doubles) <- max_i |X(i, j)|, a NaN showing: the ||x_j||_inf that scales a forward bound.  Not in the reference:
  * cholinv.hpp stops at R and R^-1.  n == 0: zeros.  No workspace. */
 int capi_dcolamax(capi_handle_t h, int64_t n, int64_t r, const double* X, int64_t ldx, double* colmax);
+/* capi_dcolnorm2: out[j] (DEVICE, r doubles) <- sum_i X(i, j)^2, a NaN showing: with X = R^-T B the quadratic forms b_j^T A^-1 b_j
+ * (cholesky::cholinv::quadratic_forms).  Not in the reference: cholinv.hpp stops at R and R^-1.  capi_dcolamax's sibling: one workgroup per column,
+ * one fixed order of the sum.  n == 0: zeros.  No workspace. */
+int capi_dcolnorm2(capi_handle_t h, int64_t n, int64_t r, const double* X, int64_t ldx, double* out);
+/* ---- reductions over the cholinv factors themselves (cholesky::cholinv::inverse_diagonal, log_determinant).  Not in the reference: cholinv.hpp stops
+ * at R and R^-1. ----
+ * capi_dtri_rownorm2: out[i] (DEVICE, m doubles) <- beta out[i] + sum_j T(i, j)^2: with T = R^-1 the diagonal of A^-1.  Not in the reference:
+ * cholinv.hpp stops at R and R^-1.  T is an m x n block addressed exactly as capi_dtrmm_thin addresses it: shape CAPI_RECT, or CAPI_UPPERTRI with
+ * m == n (the upper triangle incl. the diagonal); ldt >= m is column-major, ldt == 0 a block inside a PACKED upper triangle whose first column is the
+ * triangle's column col0 (T points at the block's first element; offsets are 64-bit).  Nothing below the diagonal is read into the result: it may hold
+ * NaN (inside the tiles that the diagonal crosses the unwanted entries are removed by a select, never multiplied by zero).  beta == 0: out is not
+ * read.  n == 0: out <- beta out.  m == 0: nothing happens.  Bad arguments: CAPI_EINVAL before any launch, nothing is touched.  T is read from HBM once
+ * per call, through capi_dtrmm_thin's NOTRANS partition (csrc/tri_thin_plan.h: the same tiles, the same slices by equal bytes); per-slice partial sums
+ * are combined in a fixed order (bit-identical runs, no atomics).  Workspace: (slices + ceil(m / 256)) x 256 doubles of the handle's workspace. */
+int capi_dtri_rownorm2(capi_handle_t h, int shape, int64_t m, int64_t n, const double* T, int64_t ldt, int64_t col0, double beta, double* out);
+/* capi_dtri_logdiag: out[0] (DEVICE) <- sum_i log T(i, i) for the upper triangular T of order n, addressed as capi_dtrsm_thin addresses it (ldt >= n, or
+ * ldt == 0 and col0): with T = R half the log-determinant of A.  Not in the reference: cholinv.hpp stops at R and R^-1.  Only the diagonal is read.  No
+ * sign check: a non-positive or NaN diagonal entry gives -Inf or NaN in the sum.  n == 0: 0.  One workgroup; a thread adds the entries tid, tid + 256,
+ * .., and the 256 sums meet pairwise in a fixed order (bit-identical runs).  No workspace. */
+int capi_dtri_logdiag(capi_handle_t h, int64_t n, const double* T, int64_t ldt, int64_t col0, double* out);
 /* capi_dlacn_block: the Hager-Higham estimator of a 1-norm (LAPACK dlacn2, Higham's refinements included) for r operators at once, by reverse
  * communication.  Not in the reference: cholinv.hpp stops at R and R^-1.  Column j estimates the 1-norm of diag(Wt(:, j)) Z -- which is
  * || Z diag(Wt(:, j)) ||_inf, dporfs's bound on || |Z| w ||_inf -- for a SYMMETRIC operator Z that the caller applies (cholinv: Z = A^-1);
