@@ -104,6 +104,10 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // rb = 1 or 2 planes of 16 columns (rpad = 16 rb)
 #define CAPI_REQUIRE_THIN_R(h, r) CAPI_REQUIRE(h, (r) >= 1 && (r) <= CAPI_TS_MAX_RHS, "r: 1 <= r <= CAPI_TS_MAX_RHS (32) columns per call")
 static inline int capi_thin_rb(int64_t r) { return r > 16 ? 2 : 1; }
+// a rows x cols view (ldt, col0) as tri_thin_plan::tri_view reads it; `rows` is named in the refusal as the caller spells it (m or n)
+#define CAPI_REQUIRE_TRI_VIEW(h, rows, cols, ldt, col0)                                                                  \
+  CAPI_REQUIRE(h, (ldt) == 0 ? ((col0) >= 0 && (col0) + (cols) < (1LL << 31)) : (ldt) >= ((rows) > 1 ? (rows) : 1), \
+               "ldt >= " #rows ", or ldt == 0 and col0 >= 0 for a view into a packed triangle")
 // CUs the selected stream may use: its CU mask's, or all
 static inline int capi_stream_cus(capi_handle_t h) { return h->cu_of[h->cur] > 0 ? h->cu_of[h->cur] : h->num_cu; }
 

@@ -18,8 +18,9 @@
 //            a strip receives its terms in a fixed order; the image goes to the block's column slot when the column of super-tiles is done
 // X_J (256 x 16) stays in LDS for a column of super-tiles, X_I is double-buffered per super-tile; A's pieces are double-buffered in registers, one
 // step ahead (one loop body: the prefetched set is moved, not a second copy of the body with the sets swapped -- that copy spilt 300 VGPRs).
-// A second launch adds the p + 1 slots of every line block in a fixed order, subtracts from B and forms the squared norms per 256
-// lines, a third adds those in order: no floating-point atomics, the same bits on every run.
+// A second launch (sym_combine_kernel) adds the p + 1 slots of every line block in a fixed order, subtracts from B (adds |B|) and forms the squared
+// norms (the maxima) per 256 lines, a third adds those in order: no floating-point atomics, the same bits on every run.  sym_fused is the host's
+// side of both calls.
 // Edges (ragged blocks, the tiles the diagonal crosses): every element from a clamped address, selected afterwards (never multiplied by zero):
 // the diagonal tile gives row <= col to U X and row < col to U^T X.  Columns are loaded 16 bytes at a time from 8-byte-aligned addresses (d2u_t).
 #include "capi_internal.h"
@@ -224,49 +225,34 @@ __global__ __launch_bounds__(SY_THREADS) void resid_sym_kernel(const SymArgs p) 
 }
 
 struct SymCombineArgs {
-  const double* slab; const double* B; double* R; double* part;
-  int64_t ldb, ldr;
+  const double* slab; const double* B; double* out; double* part;
+  int64_t ldb, ldo;
   int r;
   sp::Plan P;
 };
 
-// Rout(l, j) = B(l, j) - (the p + 1 slots of l's line block, in the plan's order); part[group][j] = the squared norms over the group's 256 lines
-__global__ __launch_bounds__(sp::SUPER) void resid_sym_combine_kernel(const SymCombineArgs p) {
+// sum(l, j): the p + 1 slots of l's line block, in the plan's order.  With the group's 256 lines:
+//   ABS == false (capi_dresid_sym)   out(l, j) = B(l, j) - sum,    part[group][j] = the squared norms, sp::RPAD columns per group
+//   ABS == true  (capi_dsym_abs)     out(l, j) = sum + |B(l, j)|,  part[group][j] = the largest, CAPI_TS_MAX_RHS columns per group; B may be null
+template <bool ABS> constexpr int SY_PART_STRIDE = ABS ? (int)CAPI_TS_MAX_RHS : sp::RPAD;
+template <bool ABS>
+__global__ __launch_bounds__(sp::SUPER) void sym_combine_kernel(const SymCombineArgs p) {
   const int64_t l = (int64_t)blockIdx.x * sp::SUPER + threadIdx.x;
   const bool in = l < p.P.n;
   const int L = in ? (int)(l / p.P.bs) : 0;
   const int64_t x = in ? l - (int64_t)L * p.P.bs : 0, sd = sp::slot_doubles(p.P);
-  tt::group_colnorms<sp::RPAD, sp::SUPER>(p.r, p.part, sp::RPAD, [&](int j) {
+  auto value = [&](int j) {
     if (!in) return 0.0;
     double sum = 0.0;
     for (int k = 0; k <= p.P.p; ++k) sum += p.slab[(int64_t)sp::contribution(p.P, L, k) * sd + (int64_t)j * p.P.bs + x];
-    const double v = p.B[l + (int64_t)j * p.ldb] - sum;
-    if (p.R) p.R[l + (int64_t)j * p.ldr] = v;
+    double v;
+    if constexpr (ABS) v = p.B ? sum + fabs(p.B[l + (int64_t)j * p.ldb]) : sum;
+    else v = p.B[l + (int64_t)j * p.ldb] - sum;
+    if (p.out) p.out[l + (int64_t)j * p.ldo] = v;
     return v;
-  });
-}
-
-struct SymAbsCombineArgs {
-  const double* slab; const double* B; double* W; double* part;
-  int64_t ldb, ldw;
-  int r;
-  sp::Plan P;
-};
-
-// capi_dsym_abs: W(l, j) = (the p + 1 slots of l's line block, in the plan's order) + |B(l, j)|; part[group][j] = the largest over the group's 256 lines
-__global__ __launch_bounds__(sp::SUPER) void sym_abs_combine_kernel(const SymAbsCombineArgs p) {
-  const int64_t l = (int64_t)blockIdx.x * sp::SUPER + threadIdx.x;
-  const bool in = l < p.P.n;
-  const int L = in ? (int)(l / p.P.bs) : 0;
-  const int64_t x = in ? l - (int64_t)L * p.P.bs : 0, sd = sp::slot_doubles(p.P);
-  tt::group_colmax<sp::RPAD, sp::SUPER>(p.r, p.part, (int)CAPI_TS_MAX_RHS, [&](int j) {
-    if (!in) return 0.0;
-    double sum = 0.0;
-    for (int k = 0; k <= p.P.p; ++k) sum += p.slab[(int64_t)sp::contribution(p.P, L, k) * sd + (int64_t)j * p.P.bs + x];
-    const double v = p.B ? sum + fabs(p.B[l + (int64_t)j * p.ldb]) : sum;
-    if (p.W) p.W[l + (int64_t)j * p.ldw] = v;
-    return v;
-  });
+  };
+  if constexpr (ABS) tt::group_colmax<sp::RPAD, sp::SUPER>(p.r, p.part, SY_PART_STRIDE<ABS>, value);
+  else tt::group_colnorms<sp::RPAD, sp::SUPER>(p.r, p.part, SY_PART_STRIDE<ABS>, value);
 }
 
 // the two-pass route's last step: W = U X + U^T X counted the diagonal twice.  Rout(l, j) = B(l, j) - (W(l, j) - A(l, l) X(l, j)); part as above,
@@ -289,6 +275,35 @@ __global__ __launch_bounds__(sp::SUPER) void resid_sym_finish_kernel(const doubl
 // diagonal's correction.  Measured (profiles/resid_sym.txt): the fused kernel ties with it at r = 1 and loses at r = 8 (4 % at n = 32768, 8 % at
 // 16384) and at r = 32 (1.4 x: it needs two passes of 16 columns itself); between 1 and 8 nothing is measured.
 constexpr int SY_TWO_PASS_FROM = 8;
+
+// The fused route of both calls, n > 0: slabs and the groups' parts in the first workspace block, resid_sym_kernel<ABS> and its combine for 16 columns
+// (sym_thin_plan::RPAD) a pass (the triangle is read once per pass, the slab reused in stream order), the parts' sum or maximum into col (may be null)
+template <bool ABS>
+int sym_fused(capi_handle_t h, int64_t n, int64_t r, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B, int64_t ldb, double* out,
+              int64_t ldo, double* col) {
+  constexpr int STRIDE = SY_PART_STRIDE<ABS>;
+  const int64_t groups = cdiv(n, sp::SUPER);
+  const sp::Plan P = sp::make_plan(n, capi_stream_cus(h));
+  void* pv = nullptr;
+  const int rc = capi_ws_get(h, sizeof(double) * (size_t)(sp::slab_doubles(P) + groups * STRIDE), &pv);
+  if (rc != CAPI_OK) return rc;
+  double* slab = (double*)pv;
+  double* part = slab + sp::slab_doubles(P);
+  CAPI_RAISE_LDS_LIMIT(h, ABS ? CAPI_ATTR_SYM_ABS : CAPI_ATTR_RESID_SYM, resid_sym_kernel<ABS>, SY_LDS);
+  for (int64_t j0 = 0; j0 < r; j0 += sp::RPAD) {
+    const int rp = (int)sp::min64(sp::RPAD, r - j0);
+    const SymArgs p{A, X + j0 * ldx, slab, lda, ldx, rp, P};
+    hipLaunchKernelGGL(resid_sym_kernel<ABS>, dim3((unsigned)sp::num_blocks(P)), dim3(SY_THREADS), SY_LDS, h->stream, p);
+    const SymCombineArgs cp{slab, B ? B + j0 * ldb : nullptr, out ? out + j0 * ldo : nullptr, col ? part + j0 : nullptr, ldb, ldo, rp, P};
+    hipLaunchKernelGGL(sym_combine_kernel<ABS>, dim3((unsigned)groups), dim3(sp::SUPER), 0, h->stream, cp);
+  }
+  if (col) {
+    if (ABS) hipLaunchKernelGGL(tt::colmax_kernel<>, dim3(1), dim3(64), 0, h->stream, (const double*)part, groups, STRIDE, (int)r, col);
+    else hipLaunchKernelGGL(tt::colnorms_kernel<>, dim3(1), dim3(64), 0, h->stream, (const double*)part, groups, STRIDE, (int)r, col);
+  }
+  CAPI_HIP_CHECK(h, hipGetLastError());
+  return CAPI_OK;
+}
 
 }  // namespace
 
@@ -324,26 +339,7 @@ int capi_dresid_sym(capi_handle_t h, int64_t n, int64_t r, const double* A, int6
     CAPI_HIP_CHECK(h, hipGetLastError());
     return CAPI_OK;
   }
-  const sp::Plan P = sp::make_plan(n, capi_stream_cus(h));
-  void* pv = nullptr;
-  int rc = capi_ws_get(h, sizeof(double) * (size_t)(sp::slab_doubles(P) + groups * sp::RPAD), &pv);
-  if (rc != CAPI_OK) return rc;
-  double* slab = (double*)pv;
-  double* part = slab + sp::slab_doubles(P);
-  CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_RESID_SYM, resid_sym_kernel<false>, SY_LDS);
-  SymArgs p;
-  p.A = A; p.X = X; p.slab = slab;
-  p.lda = lda; p.ldx = ldx;
-  p.r = (int)r; p.P = P;
-  hipLaunchKernelGGL(resid_sym_kernel<false>, dim3((unsigned)sp::num_blocks(P)), dim3(SY_THREADS), SY_LDS, h->stream, p);
-  SymCombineArgs cp;
-  cp.slab = slab; cp.B = B; cp.R = Rout; cp.part = colnorm2 ? part : nullptr;
-  cp.ldb = ldb; cp.ldr = ldr;
-  cp.r = (int)r; cp.P = P;
-  hipLaunchKernelGGL(resid_sym_combine_kernel, dim3((unsigned)groups), dim3(sp::SUPER), 0, h->stream, cp);
-  if (colnorm2) hipLaunchKernelGGL(tt::colnorms_kernel<>, dim3(1), dim3(64), 0, h->stream, (const double*)part, groups, sp::RPAD, (int)r, colnorm2);
-  CAPI_HIP_CHECK(h, hipGetLastError());
-  return CAPI_OK;
+  return sym_fused<false>(h, n, r, A, lda, X, ldx, B, ldb, Rout, ldr, colnorm2);
 }
 
 int capi_dsym_abs(capi_handle_t h, int64_t n, int64_t r, const double* A, int64_t lda, const double* X, int64_t ldx, const double* B, int64_t ldb,
@@ -353,36 +349,12 @@ int capi_dsym_abs(capi_handle_t h, int64_t n, int64_t r, const double* A, int64_
   CAPI_REQUIRE(h, n >= 0 && n < (1LL << 31) && lda < (1LL << 24), "n / lda (lda < 2^24: 32 columns are addressed by 32-bit byte offsets)");
   CAPI_REQUIRE(h, n == 0 || (A && X && lda >= n && ldx >= n && (!B || ldb >= n) && (!W || ldw >= n)), "A/lda/X/ldx/B/ldb/W/ldw");
   CAPI_REQUIRE(h, !W || W != X, "W must not alias X");
-  const int64_t groups = cdiv(n, sp::SUPER);
   if (n == 0) {
     if (colmax) hipLaunchKernelGGL(tt::colmax_kernel<>, dim3(1), dim3(64), 0, h->stream, (const double*)nullptr, (int64_t)0, (int)CAPI_TS_MAX_RHS, (int)r, colmax);
     CAPI_HIP_CHECK(h, hipGetLastError());
     return CAPI_OK;
   }
-  const sp::Plan P = sp::make_plan(n, capi_stream_cus(h));
-  void* pv = nullptr;
-  int rc = capi_ws_get(h, sizeof(double) * (size_t)(sp::slab_doubles(P) + groups * CAPI_TS_MAX_RHS), &pv);
-  if (rc != CAPI_OK) return rc;
-  double* slab = (double*)pv;
-  double* part = slab + sp::slab_doubles(P);
-  CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_SYM_ABS, resid_sym_kernel<true>, SY_LDS);
-  // the fused kernel holds 16 columns (sym_thin_plan::RPAD): the triangle is read once per pass, the slab is reused in stream order
-  for (int64_t j0 = 0; j0 < r; j0 += sp::RPAD) {
-    const int rp = (int)sp::min64(sp::RPAD, r - j0);
-    SymArgs p;
-    p.A = A; p.X = X + j0 * ldx; p.slab = slab;
-    p.lda = lda; p.ldx = ldx;
-    p.r = rp; p.P = P;
-    hipLaunchKernelGGL(resid_sym_kernel<true>, dim3((unsigned)sp::num_blocks(P)), dim3(SY_THREADS), SY_LDS, h->stream, p);
-    SymAbsCombineArgs cp;
-    cp.slab = slab; cp.B = B ? B + j0 * ldb : nullptr; cp.W = W ? W + j0 * ldw : nullptr; cp.part = colmax ? part + j0 : nullptr;
-    cp.ldb = ldb; cp.ldw = ldw;
-    cp.r = rp; cp.P = P;
-    hipLaunchKernelGGL(sym_abs_combine_kernel, dim3((unsigned)groups), dim3(sp::SUPER), 0, h->stream, cp);
-  }
-  if (colmax) hipLaunchKernelGGL(tt::colmax_kernel<>, dim3(1), dim3(64), 0, h->stream, (const double*)part, groups, (int)CAPI_TS_MAX_RHS, (int)r, colmax);
-  CAPI_HIP_CHECK(h, hipGetLastError());
-  return CAPI_OK;
+  return sym_fused<true>(h, n, r, A, lda, X, ldx, B, ldb, W, ldw, colmax);
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 // T is read from HBM once and the call is bound by that stream; the arithmetic goes to v_mfma_f64_16x16x4_f64 with the r columns padded to 16 or 32.
 // The work is cut into tiles of 256 output lines x 32 contraction indices and dealt to one workgroup per CU by equal BYTES (tri_thin_plan.h): the
 // lines of a triangle have lengths 1..n.  A workgroup walks its consecutive tiles; the 256 x rpad partial sums of every group of lines it
-// touches go to a slab of its own, and a second launch adds a group's slabs in slice order: no floating-point atomics, the same bits on every run.
+// touches go to a slab of its own and are added by a second launch (tri_slab.h: the prologue, the slot rule, the combine).
 // The thin operand is stationary in LDS, 256 contraction indices at a time in two halves: the next block is fetched while the last tile of the
 // current one is multiplied, one barrier per block.  T's pieces are double-buffered in registers, one tile (8 x 16 bytes per lane) ahead.  A wave's
 // 32 x 32 part of a tile is multiplied in the row-dot form of thin_tile.h for NOTRANS and in its column-dot form for TRANS.
@@ -20,12 +20,14 @@
 #include <type_traits>
 #include "capi_internal.h"
 #include "thin_tile.h"
+#include "tri_slab.h"
 #include "tri_thin_plan.h"
 
 namespace {
 
 namespace tp = tri_thin_plan;
 namespace tt = thin_tile;
+namespace ts = tri_slab;
 using tt::d2_t;
 using tt::d2u_t;
 using tt::d4_t;
@@ -52,6 +54,7 @@ __global__ __launch_bounds__(TT_THREADS) void trmm_thin_kernel(const ThinArgs p)
   if (p0 >= p1) return;
   const bool tri = p.P.tri;
   const int64_t m = p.P.m, n = p.P.n;
+  // tp::tri_view::col on the fields where they lie: held as a tri_view they load in another order and the kernels come out in another schedule
   auto colptr = [&](int64_t j) { return p.ldt > 0 ? p.T + j * p.ldt : p.T + tp::packed_col_offset(p.col0, j); };
   auto valid = [&](int64_t row, int64_t col) { return row < m && col < n && (!tri || row <= col); };
 
@@ -128,9 +131,9 @@ __global__ __launch_bounds__(TT_THREADS) void trmm_thin_kernel(const ThinArgs p)
     else tt::mfma_col_dots<RB>(acc, L + (kb + 2 * g4) * 16 + l16, TT_BLK * 16, cur);
     __builtin_amdgcn_s_setprio(0);
   };
-  // the group's partial sums: slab slot s + g (unique: the slices' tile ranges are consecutive), [16 RB columns][256 lines]
+  // the group's partial sums, to this slice's slab for it: [16 RB columns][256 lines]
   auto flush = [&](int64_t g) {
-    double* sl = p.slab + ((int64_t)s + g) * (tp::GROUP * 16 * RB);
+    double* sl = p.slab + ts::slab_offset(s, g, 16 * RB);
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -185,36 +188,6 @@ __global__ __launch_bounds__(TT_THREADS) void trmm_thin_kernel(const ThinArgs p)
   }
 }
 
-struct CombineArgs {
-  const double* slab; double* C;
-  int64_t ldc;
-  double alpha, beta;
-  int r, rpad, S;
-  tp::Plan P;
-  int64_t pos[tp::MAX_SLICES + 1];
-};
-
-// C(l, j) = alpha (the slabs of l's group, in slice order) + beta C(l, j); beta == 0 does not read C
-__global__ __launch_bounds__(tp::GROUP) void trmm_thin_combine_kernel(const CombineArgs p) {
-  const int64_t g = blockIdx.x, l = g * tp::GROUP + threadIdx.x;
-  if (l >= p.P.lines) return;
-  int sa = 0, sb = -1;
-  if (p.S > 0) {
-    const int64_t t0 = tp::tiles_before(p.P, g), t1 = tp::tiles_before(p.P, g + 1);
-    while (p.pos[sa + 1] <= t0) ++sa;                                    // the slice that holds the group's first tile
-    sb = sa;
-    while (sb + 1 < p.S && p.pos[sb + 1] < t1) ++sb;                     // .. and its last
-  }
-  for (int j = 0; j < p.r; ++j) {
-    double sum = 0.0;
-    for (int s = sa; s <= sb; ++s)
-      if (p.pos[s] < p.pos[s + 1]) sum += p.slab[(((int64_t)s + g) * p.rpad + j) * tp::GROUP + threadIdx.x];
-    double v = p.alpha * sum;
-    if (p.beta != 0.0) v += p.beta * p.C[l + (int64_t)j * p.ldc];
-    p.C[l + (int64_t)j * p.ldc] = v;
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -227,40 +200,32 @@ int capi_dtrmm_thin(capi_handle_t h, int shape, int trans, int64_t m, int64_t n,
   CAPI_REQUIRE(h, trans == CAPI_NOTRANS || trans == CAPI_TRANS, "trans");
   CAPI_REQUIRE(h, m >= 0 && n >= 0 && m < (1LL << 31) && n < (1LL << 31), "m / n");
   CAPI_REQUIRE(h, shape != CAPI_UPPERTRI || m == n, "CAPI_UPPERTRI: m == n");
-  CAPI_REQUIRE(h, ldt == 0 ? (col0 >= 0 && col0 + n < (1LL << 31)) : ldt >= (m > 1 ? m : 1), "ldt >= m, or ldt == 0 and col0 >= 0 for a view into a packed triangle");
+  CAPI_REQUIRE_TRI_VIEW(h, m, n, ldt, col0);
   const int64_t lines = trans ? n : m, depth = trans ? m : n;
   CAPI_REQUIRE(h, ldb >= (depth > 1 ? depth : 1) && ldc >= (lines > 1 ? lines : 1), "ldb / ldc");
   CAPI_REQUIRE(h, lines == 0 || C, "C");
   CAPI_REQUIRE(h, lines == 0 || depth == 0 || (T && B && B != C), "T / B (C must not alias B)");
   if (lines == 0) return CAPI_OK;
-  const int rb = capi_thin_rb(r), rpad = 16 * rb;
-  CombineArgs cp;
-  cp.P = tp::make_plan(shape == CAPI_UPPERTRI ? tp::UPPERTRI : tp::RECT, trans, m, n);
-  const int S = tp::make_slices(cp.P, capi_stream_cus(h), cp.pos);
-  double* slab = nullptr;
-  if (S > 0) {
-    void* pv = nullptr;
-    int rc = capi_ws_get(h, sizeof(double) * (size_t)((S + cp.P.ngroups) * tp::GROUP * rpad), &pv);
-    if (rc != CAPI_OK) return rc;
-    slab = (double*)pv;
-    ThinArgs p;
-    p.T = T; p.B = B; p.slab = slab;
+  const int rb = capi_thin_rb(r);
+  ts::CombineArgs cp;
+  ThinArgs p;
+  const int rc = ts::plan_slabs(h, shape, trans, m, n, 16 * rb, &cp, &p);
+  if (rc != CAPI_OK) return rc;
+  if (cp.S > 0) {
+    p.T = T; p.B = B;
     p.ldt = ldt; p.col0 = col0; p.ldb = ldb;
-    p.r = (int)r; p.S = S; p.P = cp.P;
-    memcpy(p.pos, cp.pos, sizeof(int64_t) * (size_t)(S + 1));
+    p.r = (int)r;
     const size_t lds = sizeof(double) * 2 * (size_t)rb * TT_BLK * 16;
     const int v = 2 * (rb - 1) + (trans ? 1 : 0);
 #define TT_LAUNCH(RB, TR)                                                                                                  \
     do {                                                                                                                   \
       CAPI_RAISE_LDS_LIMIT(h, CAPI_ATTR_TRMM_THIN0 + v, (trmm_thin_kernel<RB, TR>), lds);                                   \
-      hipLaunchKernelGGL((trmm_thin_kernel<RB, TR>), dim3((unsigned)S), dim3(TT_THREADS), lds, h->stream, p);               \
+      hipLaunchKernelGGL((trmm_thin_kernel<RB, TR>), dim3((unsigned)cp.S), dim3(TT_THREADS), lds, h->stream, p);            \
     } while (0)
     if (v == 0) TT_LAUNCH(1, false); else if (v == 1) TT_LAUNCH(1, true); else if (v == 2) TT_LAUNCH(2, false); else TT_LAUNCH(2, true);
 #undef TT_LAUNCH
   }
-  cp.slab = slab; cp.C = C; cp.ldc = ldc; cp.alpha = alpha; cp.beta = beta;
-  cp.r = (int)r; cp.rpad = rpad; cp.S = S;
-  hipLaunchKernelGGL(trmm_thin_combine_kernel, dim3((unsigned)cp.P.ngroups), dim3(tp::GROUP), 0, h->stream, cp);
+  ts::combine(h, cp, (int)r, alpha, beta, C, ldc);
   CAPI_HIP_CHECK(h, hipGetLastError());
   return CAPI_OK;
 }

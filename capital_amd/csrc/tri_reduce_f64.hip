@@ -4,23 +4,24 @@
 //   capi_dtri_rownorm2   out[i] <- beta out[i] + sum_j T(i, j)^2      the diagonal of A^-1 from the rows of R^-1
 //   capi_dtri_logdiag    out[0] <- sum_i log T(i, i)                  half the log-determinant of A from R
 //
-// capi_dtri_rownorm2 is the NOTRANS thin product of tri_apply_f64.hip with T's own entries standing in for the thin operand: the same tiles of 256 lines
-// x 32 columns, the same slices by equal bytes (tri_thin_plan.h: make_plan(.., NOTRANS, ..) and make_slices, nothing of its own), the same pieces per
-// lane (rows 2 l16, + 1 of column 4 q + g4 of the wave's 32 x 32 part), double-buffered in registers one tile ahead.  T is read from HBM once and the
-// call is bound by that stream; there is no LDS, no barrier and no MFMA, so the waves of a workgroup need not keep step: each walks the whole tiles of
-// its own 32 lines in a loop of its own (the diagonal meets every wave at another tile).  A lane squares its 16 elements into two sums, and where its
-// workgroup leaves a group of lines the four lanes of a row pair meet in a fixed butterfly.  The 256 partial sums of every group of lines a workgroup touches go to
-// a slab of their own, and a second launch adds a group's slabs in slice order: no floating-point atomics, the same bits on every run.
+// capi_dtri_rownorm2 is the NOTRANS thin product of tri_apply_f64.hip with T's own entries standing in for the thin operand: its plan and slices
+// (tri_thin_plan.h), its prologue, slabs and combine (tri_slab.h, one column), its pieces per lane (rows 2 l16, + 1 of column 4 q + g4 of the wave's
+// 32 x 32 part), double-buffered in registers one tile ahead.  T is read from HBM once and the call is bound by that stream; there is no LDS, no barrier
+// and no MFMA, so the waves of a workgroup need not keep step: each walks the whole tiles of its own 32 lines in a loop of its own (the diagonal meets
+// every wave at another tile).  A lane squares its 16 elements into two sums, and where its workgroup leaves a group of lines the four lanes of a row
+// pair meet in a fixed butterfly.
 // Edges (ragged tiles, the tiles the diagonal crosses): every element is loaded from a clamped address and SELECTED afterwards, as in the product;
 // nothing below the diagonal or outside the block is read into a sum, whatever it holds.
 #include "capi_internal.h"
 #include "thin_tile.h"
+#include "tri_slab.h"
 #include "tri_thin_plan.h"
 
 namespace {
 
 namespace tp = tri_thin_plan;
 namespace tt = thin_tile;
+namespace ts = tri_slab;
 using tt::d2_t;
 using tt::d2u_t;
 
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(TR_THREADS) void tri_rownorm2_kernel(const RowNormA
   if (p0 >= p1) return;
   const bool tri = p.P.tri, packed = p.ldt == 0;
   const int64_t m = p.P.m, n = p.P.n;
-  auto colptr = [&](int64_t j) { return packed ? p.T + tp::packed_col_offset(p.col0, j) : p.T + j * p.ldt; };
+  auto colptr = [&](int64_t j) { return packed ? p.T + tp::packed_col_offset(p.col0, j) : p.T + j * p.ldt; };   // tp::tri_view::col, as in trmm_thin_kernel
   auto valid = [&](int64_t row, int64_t col) { return row < m && col < n && (!tri || row <= col); };
 
   d2_t acc = (d2_t){0.0, 0.0};                   // rows 2 l16, + 1 of the wave's 32 lines, over this lane's columns
@@ -100,12 +101,12 @@ __global__ __launch_bounds__(TR_THREADS) void tri_rownorm2_kernel(const RowNormA
     if (c + 1 < c1) { tload(pb); square(pa); square(pb); }
     else square(pa);
   };
-  // the group's partial sums: slab slot s + g (unique: the slices' tile ranges are consecutive), 256 lines
+  // the group's partial sums, to this slice's slab for it: 256 lines
   auto flush = [&](int64_t g) {
     d2_t v = acc;
     v.x += __shfl_xor(v.x, 16); v.y += __shfl_xor(v.y, 16);
     v.x += __shfl_xor(v.x, 32); v.y += __shfl_xor(v.y, 32);
-    if (g4 == 0) *(d2_t*)(p.slab + ((int64_t)s + g) * tp::GROUP + 32 * w + 2 * l16) = v;
+    if (g4 == 0) *(d2_t*)(p.slab + ts::slab_offset(s, g, 1) + 32 * w + 2 * l16) = v;
     acc = (d2_t){0.0, 0.0};
   };
 
@@ -128,40 +129,14 @@ __global__ __launch_bounds__(TR_THREADS) void tri_rownorm2_kernel(const RowNormA
   }
 }
 
-struct RowNormCombineArgs {
-  const double* slab; double* out;
-  double beta;
-  int S;
-  tp::Plan P;
-  int64_t pos[tp::MAX_SLICES + 1];
-};
-
-// out[l] = (the slabs of l's group, in slice order) + beta out[l]; beta == 0 does not read out
-__global__ __launch_bounds__(tp::GROUP) void tri_rownorm2_combine_kernel(const RowNormCombineArgs p) {
-  const int64_t g = blockIdx.x, l = g * tp::GROUP + threadIdx.x;
-  if (l >= p.P.lines) return;
-  int sa = 0, sb = -1;
-  if (p.S > 0) {
-    const int64_t t0 = tp::tiles_before(p.P, g), t1 = tp::tiles_before(p.P, g + 1);
-    while (p.pos[sa + 1] <= t0) ++sa;                                    // the slice that holds the group's first tile
-    sb = sa;
-    while (sb + 1 < p.S && p.pos[sb + 1] < t1) ++sb;                     // .. and its last
-  }
-  double sum = 0.0;
-  for (int s = sa; s <= sb; ++s)
-    if (p.pos[s] < p.pos[s + 1]) sum += p.slab[((int64_t)s + g) * tp::GROUP + threadIdx.x];
-  if (p.beta != 0.0) sum += p.beta * p.out[l];
-  p.out[l] = sum;
-}
-
 constexpr int LD_THREADS = 256;
 
 // One workgroup.  A thread adds the logarithms of the entries tid, tid + 256, ..; the 256 sums meet pairwise: a butterfly inside the wave, then the
 // four waves as (0 + 1) + (2 + 3)
-__global__ __launch_bounds__(LD_THREADS) void tri_logdiag_kernel(int64_t n, const double* __restrict__ T, int64_t ldt, int64_t col0, double* __restrict__ out) {
+__global__ __launch_bounds__(LD_THREADS) void tri_logdiag_kernel(int64_t n, const tp::tri_view T, double* __restrict__ out) {
   __shared__ double red[4];
   double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += LD_THREADS) s += log(*(ldt > 0 ? T + i * ldt + i : T + tp::packed_col_offset(col0, i) + i));
+  for (int64_t i = threadIdx.x; i < n; i += LD_THREADS) s += log(*T.at(i, i));
   s = tt::butterfly_sum<64>(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -177,28 +152,19 @@ int capi_dtri_rownorm2(capi_handle_t h, int shape, int64_t m, int64_t n, const d
   CAPI_REQUIRE(h, shape == CAPI_RECT || shape == CAPI_UPPERTRI, "shape: CAPI_RECT or CAPI_UPPERTRI");
   CAPI_REQUIRE(h, m >= 0 && n >= 0 && m < (1LL << 31) && n < (1LL << 31), "m / n");
   CAPI_REQUIRE(h, shape != CAPI_UPPERTRI || m == n, "CAPI_UPPERTRI: m == n");
-  CAPI_REQUIRE(h, ldt == 0 ? (col0 >= 0 && col0 + n < (1LL << 31)) : ldt >= (m > 1 ? m : 1), "ldt >= m, or ldt == 0 and col0 >= 0 for a view into a packed triangle");
+  CAPI_REQUIRE_TRI_VIEW(h, m, n, ldt, col0);
   CAPI_REQUIRE(h, m == 0 || out, "out");
   CAPI_REQUIRE(h, m == 0 || n == 0 || T, "T");
   if (m == 0) return CAPI_OK;
-  RowNormCombineArgs cp;
-  cp.P = tp::make_plan(shape == CAPI_UPPERTRI ? tp::UPPERTRI : tp::RECT, CAPI_NOTRANS, m, n);
-  const int S = tp::make_slices(cp.P, capi_stream_cus(h), cp.pos);
-  double* slab = nullptr;
-  if (S > 0) {
-    void* pv = nullptr;
-    int rc = capi_ws_get(h, sizeof(double) * (size_t)((S + cp.P.ngroups) * tp::GROUP), &pv);
-    if (rc != CAPI_OK) return rc;
-    slab = (double*)pv;
-    RowNormArgs p;
-    p.T = T; p.slab = slab;
-    p.ldt = ldt; p.col0 = col0;
-    p.S = S; p.P = cp.P;
-    memcpy(p.pos, cp.pos, sizeof(int64_t) * (size_t)(S + 1));
-    hipLaunchKernelGGL(tri_rownorm2_kernel, dim3((unsigned)S), dim3(TR_THREADS), 0, h->stream, p);
+  ts::CombineArgs cp;
+  RowNormArgs p;
+  const int rc = ts::plan_slabs(h, shape, CAPI_NOTRANS, m, n, 1, &cp, &p);
+  if (rc != CAPI_OK) return rc;
+  if (cp.S > 0) {
+    p.T = T; p.ldt = ldt; p.col0 = col0;
+    hipLaunchKernelGGL(tri_rownorm2_kernel, dim3((unsigned)cp.S), dim3(TR_THREADS), 0, h->stream, p);
   }
-  cp.slab = slab; cp.out = out; cp.beta = beta; cp.S = S;
-  hipLaunchKernelGGL(tri_rownorm2_combine_kernel, dim3((unsigned)cp.P.ngroups), dim3(tp::GROUP), 0, h->stream, cp);
+  ts::combine(h, cp, 1, 1.0, beta, out, m);                               // one column of m lines; 1.0 * sum is sum
   CAPI_HIP_CHECK(h, hipGetLastError());
   return CAPI_OK;
 }
@@ -206,8 +172,8 @@ int capi_dtri_rownorm2(capi_handle_t h, int shape, int64_t m, int64_t n, const d
 int capi_dtri_logdiag(capi_handle_t h, int64_t n, const double* T, int64_t ldt, int64_t col0, double* out) {
   CAPI_REQUIRE(h, h, "null handle");
   CAPI_REQUIRE(h, n >= 0 && n < (1LL << 31) && out && (n == 0 || T), "n / T / out");
-  CAPI_REQUIRE(h, ldt == 0 ? (col0 >= 0 && col0 + n < (1LL << 31)) : ldt >= (n > 1 ? n : 1), "ldt >= n, or ldt == 0 and col0 >= 0 for a view into a packed triangle");
-  hipLaunchKernelGGL(tri_logdiag_kernel, dim3(1), dim3(LD_THREADS), 0, h->stream, n, T, ldt, col0, out);
+  CAPI_REQUIRE_TRI_VIEW(h, n, n, ldt, col0);
+  hipLaunchKernelGGL(tri_logdiag_kernel, dim3(1), dim3(LD_THREADS), 0, h->stream, n, tp::tri_view{T, ldt, col0}, out);
   CAPI_HIP_CHECK(h, hipGetLastError());
   return CAPI_OK;
 }

@@ -5,7 +5,8 @@
 //   capi_dtrsm_thin   B <- op(T)^-1 B      no inverse of T or of a block of it is formed; reciprocals of diagonal ENTRIES only
 //
 // The call runs the step list of trsm_thin_plan.h on the handle's stream: leaves (diagonal sub-triangles of order <= LEAF, the kernel below, one
-// workgroup each) and rectangular products (capi_dtrmm_thin, alpha = -1, beta = 1, between disjoint rows of B).  Every element of T belongs to one
+// workgroup each) and rectangular products (capi_dtrmm_thin, alpha = -1, beta = 1, between disjoint rows of B), each on a sub-view of T
+// (tri_thin_plan.h: tri_view::sub).  Every element of T belongs to one
 // step, so T is read from HBM once.  Ordering is by kernel boundaries alone: no flag is waited on, no cooperative launch, no atomics, and every sum
 // has a fixed order -- the same bits on every run.
 //
@@ -42,8 +43,9 @@ constexpr int TS_NT = 3;                         // tile waves beside the solver
 constexpr size_t ts_lds_doubles(int RB) { return (size_t)RB * TS_XR * 16 + (size_t)TS_NT * 16 * RB * TS_BS + TS_BS * TS_DP + TS_BS; }
 
 struct SolveArgs {
-  const double* T; double* B;
-  int64_t ldt, col0, ldb;
+  tp::tri_view T;
+  double* B;
+  int64_t ldb;
   int n, r;
 };
 
@@ -58,7 +60,6 @@ __global__ __launch_bounds__(64 * (TS_NT + 1)) void trsm_thin_leaf_kernel(const 
   double* const Dinv = D + TS_BS * TS_DP;          // [32]
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n = p.n, nb = (n + TS_BS - 1) / TS_BS;
-  auto colptr = [&](int64_t j) { return p.ldt > 0 ? p.T + j * p.ldt : p.T + tp::packed_col_offset(p.col0, j); };
   auto blk = [&](int s) { return TR ? s : nb - 1 - s; };                  // the block solved in slot s
   auto xrow = [&](int b) { return TR ? TS_BS * b : TS_BS * (b - 1); };    // its first row in X (the block solved last is never stored)
 
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(64 * (TS_NT + 1)) void trsm_thin_leaf_kernel(const 
     for (int q = 0; q < NDQ; ++q) {
       const int e = u0 + 64 * NT * q, row = e & 31, col = (e >> 5) & 31;
       const bool in = row <= col && col < nr;
-      const double x = *(in ? colptr(TS_BS * b + col) + TS_BS * b + row : p.T);
+      const double x = *(in ? p.T.col(TS_BS * b + col) + TS_BS * b + row : p.T.T);
       dreg[q] = in ? x : (row == col ? 1.0 : 0.0);
     }
   };
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(64 * (TS_NT + 1)) void trsm_thin_leaf_kernel(const 
     for (int q = 0; q < 8; ++q) {
       const int row = rb0 + (TR ? 8 * (q & 3) + 2 * g4 : 2 * l16), col = cb0 + (TR ? 16 * (q >> 2) + l16 : 4 * q + g4);
       const bool in = col < n;
-      const d2_t x = __builtin_nontemporal_load((const d2u_t*)(colptr(in ? col : n - 1) + row));
+      const d2_t x = __builtin_nontemporal_load((const d2u_t*)(p.T.col(in ? col : n - 1) + row));
       st[q] = in ? x : (d2_t){0.0, 0.0};
     }
   };
@@ -229,22 +230,22 @@ int capi_dtrsm_thin(capi_handle_t h, int trans, int64_t n, int64_t r, const doub
   CAPI_REQUIRE_THIN_R(h, r);
   CAPI_REQUIRE(h, trans == CAPI_NOTRANS || trans == CAPI_TRANS, "trans");
   CAPI_REQUIRE(h, n >= 0 && n < (1LL << 31), "n");
-  CAPI_REQUIRE(h, ldt == 0 ? (col0 >= 0 && col0 + n < (1LL << 31)) : ldt >= (n > 1 ? n : 1), "ldt >= n, or ldt == 0 and col0 >= 0 for a view into a packed triangle");
+  CAPI_REQUIRE_TRI_VIEW(h, n, n, ldt, col0);
   CAPI_REQUIRE(h, ldb >= (n > 1 ? n : 1), "ldb");
   CAPI_REQUIRE(h, n == 0 || (T && B), "T / B");
   if (n == 0) return CAPI_OK;
   const int rb = capi_thin_rb(r), cw = r <= 4 ? 4 : (r <= 16 ? 16 : 32);
   const int v = (cw == 4 ? 0 : (cw == 16 ? 2 : 4)) + (trans ? 1 : 0);
-  // element (i, j) of the view
-  auto at = [&](int64_t i, int64_t j) { return ldt > 0 ? T + i + j * ldt : T + tp::packed_col_offset(col0, j) + i; };
+  const tp::tri_view V{T, ldt, col0};
   const int rc = sp::for_each_step(trans, 0, n, [&](const sp::Step& s) -> int {
     if (s.kind == sp::STEP_PRODUCT) {
       const int64_t in0 = trans ? s.row0 : s.col0, out0 = trans ? s.col0 : s.row0;
-      return capi_dtrmm_thin(h, CAPI_RECT, trans, s.m, s.n, r, -1.0, at(s.row0, s.col0), ldt, ldt > 0 ? 0 : col0 + s.col0, B + in0, ldb, 1.0, B + out0, ldb);
+      const tp::tri_view blk = V.sub(s.row0, s.col0);
+      return capi_dtrmm_thin(h, CAPI_RECT, trans, s.m, s.n, r, -1.0, blk.T, blk.ldt, blk.col0, B + in0, ldb, 1.0, B + out0, ldb);
     }
     SolveArgs p;
-    p.T = at(s.row0, s.col0); p.B = B + s.row0;
-    p.ldt = ldt; p.col0 = ldt > 0 ? 0 : col0 + s.col0; p.ldb = ldb;
+    p.T = V.sub(s.row0, s.col0); p.B = B + s.row0;
+    p.ldb = ldb;
     p.n = (int)s.n; p.r = (int)r;
     const size_t lds = sizeof(double) * ts_lds_doubles(rb);
 #define TS_LAUNCH(RB, CW, TR)                                                                                                        \

@@ -1,5 +1,6 @@
-// tri_thin_plan.h -- how capi_dtrmm_thin (tri_apply_f64.hip) cuts C <- alpha op(T) B + beta C into workgroup slices.  Pure arithmetic in the
-// manner of gemm_plan.h: no HIP, compiled by a host compiler too (tests/tri_thin_plan), and by hipcc for both sides.
+// tri_thin_plan.h -- how capi_dtrmm_thin (tri_apply_f64.hip) cuts C <- alpha op(T) B + beta C into workgroup slices, and tri_view, the way every
+// kernel on the cholinv factors addresses its triangle.  Pure arithmetic in the manner of gemm_plan.h: no HIP, compiled by a host compiler too
+// (tests/tri_thin_plan), and by hipcc for both sides.  What a call does around the plan (workspace, slabs, the combine launch) is in tri_slab.h.
 //
 // The m x n block T (all of it, or the upper triangle incl. the diagonal) is cut into TILES.  A tile belongs to a GROUP of 256 output lines
 // (rows of T for NOTRANS, columns for TRANS: one workgroup of 8 waves x 32 lines) and is 32 deep along the contraction index (columns for
@@ -35,6 +36,21 @@ THIN_HD inline int64_t packed_col_start(int64_t x) { return (x & 1) ? x * ((x + 
 THIN_HD inline int64_t packed_col_offset(int64_t col0, int64_t j) { return packed_col_start(col0 + j) - packed_col_start(col0); }
 // alignment class of a column that starts `start` doubles behind a 16-byte boundary: 0 = 16-byte aligned, 1 = 8-byte aligned only
 THIN_HD inline int align_class(int64_t start) { return (int)(start & 1); }
+
+// THE VIEW that the kernels on the cholinv factors take (capi_dtrmm_thin, capi_dtri_*, capi_dtrsm_thin, capi_dchud*): a block whose first element is T,
+// column-major with the leading dimension ldt > 0, or, ldt == 0, a view into a packed upper triangle whose first column is the triangle's column col0
+// (not read when ldt > 0).  Checked by CAPI_REQUIRE_TRI_VIEW (capi_internal.h); cholinv.h's image::at is the host's twin of sub()
+template <class D>
+struct tri_view_t {
+  D* T;
+  int64_t ldt, col0;
+  THIN_HD bool packed() const { return ldt == 0; }
+  THIN_HD D* col(int64_t j) const { return ldt > 0 ? T + j * ldt : T + packed_col_offset(col0, j); }     // first element of column j
+  THIN_HD D* at(int64_t i, int64_t j) const { return col(j) + i; }
+  THIN_HD tri_view_t sub(int64_t i0, int64_t j0) const { return tri_view_t{at(i0, j0), ldt, ldt > 0 ? 0 : col0 + j0}; }   // first element (i0, j0)
+};
+using tri_view = tri_view_t<const double>;
+using tri_view_rw = tri_view_t<double>;         // chud_f64.hip rewrites the triangle in place
 
 THIN_HD inline Plan make_plan(int shape, int trans, int64_t m, int64_t n) {
   Plan P;

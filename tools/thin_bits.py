@@ -1,5 +1,5 @@
-"""One SHA-256 per output array of the thin kernels (capi_dgemtn_ts, capi_dresid_ts, capi_dtrmm_thin, capi_dresid_sym) on a fixed list of cases with
-fixed seeds: run it under two builds of the library (CAPITAL_HIP_LIB) and diff the two outputs -- a refactor of these kernels leaves every line as
+"""One SHA-256 per output array of the thin kernels (capi_dgemtn_ts, capi_dresid_ts, capi_dtrmm_thin, capi_dresid_sym, capi_dtri_rownorm2,
+capi_dtri_logdiag, capi_dtrsm_thin, capi_dchud + capi_dchud_inv, capi_dsym_abs) on a fixed list of cases with fixed seeds: run it under two builds of the library (CAPITAL_HIP_LIB) and diff the two outputs -- a refactor of these kernels leaves every line as
 it is.  The shapes are the GPU tests' small ones: ragged tiles, the diagonal's tiles, r <= 16 and r > 16, both routes of capi_dresid_sym, the edge
 loaders (odd and padded leading dimensions, an unaligned base, packed storage at an odd col0).  Every output buffer is hashed whole, padding rows
 included, so a stray write shows too.
@@ -114,6 +114,117 @@ def main():
                 print(f"dresid_sym {tag} Rout-only Rout {sha(R)}")
                 h.call("capi_dresid_sym", n, r, A.data_ptr(), lda, X.data_ptr(), n + 1, B.data_ptr(), n + 2, None, 0, nrm.data_ptr())
                 print(f"dresid_sym {tag} norms-only colnorm2 {sha(nrm)}")
+
+    # ---- the triangles of the cases below: order n with a dominant positive diagonal, as a view at an odd col0 of a larger packed triangle whose other
+    # words hold values too, and column-major with a padded ld (values below the diagonal and in the padding).  Returns host arrays and view offsets ----
+    COL0 = 129
+
+    def packed_host(rng, n, scale=1.0):
+        a = scale * rng.standard_normal(pstart(COL0 + n))
+        for j in range(n):
+            e = pstart(COL0 + j) + COL0 + j
+            a[e] = 4.0 * np.sqrt(n) + abs(a[e])
+        return a, pstart(COL0) + COL0
+
+    def full_host(rng, n, ld, scale=1.0):
+        a = scale * rng.standard_normal(ld * n)
+        d = np.arange(n) * (ld + 1)
+        a[d] = 4.0 * np.sqrt(n) + np.abs(a[d])
+        return a, 0
+
+    def triangles(seed, n, scale=1.0):
+        """[(name, host array, offset of the view's first element, ldt, col0)]"""
+        hp, op = packed_host(np.random.default_rng(seed + [0]), n, scale)
+        hf, of = full_host(np.random.default_rng(seed + [1]), n, n + 3, scale)
+        return (("packed", hp, op, 0, COL0), ("full", hf, of, n + 3, 0))
+
+    # ---- capi_dtri_rownorm2, capi_dtri_logdiag ----
+    for n in (300, 777):
+        for store, host, off, ldt, c0 in triangles([7, n], n):
+            T = dev(host)
+            pT = T.data_ptr() + 8 * off
+            rng = np.random.default_rng([8, n, ldt])
+            o = out(rng, n + 2, 1)
+            h.call("capi_dtri_rownorm2", UPPERTRI, n, n, pT, ldt, c0, 0.0, o.data_ptr())
+            print(f"dtri_rownorm2 tri n{n} {store} beta0 out {sha(o)}")
+            h.call("capi_dtri_rownorm2", UPPERTRI, n, n, pT, ldt, c0, 1.0, o.data_ptr())
+            print(f"dtri_rownorm2 tri n{n} {store} beta1 out {sha(o)}")
+            ld1 = out(rng, 3, 1)
+            h.call("capi_dtri_logdiag", n, pT, ldt, c0, ld1.data_ptr())
+            print(f"dtri_logdiag n{n} {store} out {sha(ld1)}")
+            if store == "packed":
+                # a rectangle inside the packed triangle: rows 0 .. m - 1 of its columns col0 .., m <= col0
+                m = 100
+                pR = T.data_ptr() + 8 * pstart(c0)
+                o = out(rng, m + 2, 1)
+                h.call("capi_dtri_rownorm2", RECT, m, n, pR, 0, c0, 0.0, o.data_ptr())
+                print(f"dtri_rownorm2 rect {m}x{n} packed beta0 out {sha(o)}")
+                h.call("capi_dtri_rownorm2", RECT, m, n, pR, 0, c0, 1.0, o.data_ptr())
+                print(f"dtri_rownorm2 rect {m}x{n} packed beta1 out {sha(o)}")
+    for m, n in ((5, 300), (777, 129)):
+        rng = np.random.default_rng([9, m, n])
+        ld = m + 1
+        T = dev(rng.standard_normal(ld * n))
+        o = out(rng, m + 2, 1)
+        h.call("capi_dtri_rownorm2", RECT, m, n, T.data_ptr(), ld, 0, 0.0, o.data_ptr())
+        print(f"dtri_rownorm2 rect {m}x{n} full beta0 out {sha(o)}")
+        h.call("capi_dtri_rownorm2", RECT, m, n, T.data_ptr(), ld, 0, 1.0, o.data_ptr())
+        print(f"dtri_rownorm2 rect {m}x{n} full beta1 out {sha(o)}")
+
+    # ---- capi_dtrsm_thin (n = 777: two leaves and a rectangular product between them) ----
+    for n in (300, 777):
+        for store, host, off, ldt, c0 in triangles([10, n], n):
+            T = dev(host)
+            pT = T.data_ptr() + 8 * off
+            for r in (1, 5, 32):
+                for trans in (0, 1):
+                    rng = np.random.default_rng([11, n, r, trans, ldt])
+                    B = out(rng, (n + 3) * r, 1)
+                    h.call("capi_dtrsm_thin", trans, n, r, pT, ldt, c0, B.data_ptr(), n + 3)
+                    print(f"dtrsm_thin n{n} r{r} t{trans} {store} B {sha(B)}")
+
+    # ---- capi_dchud, capi_dchud_inv: T, V and the log of the factor; the inverse in one range and in two ----
+    import ctypes as C
+    for n in (300, 777):
+        for r in (1, 17, 32):
+            for sign in (1, -1):
+                for store, host, off, ldt, c0 in triangles([12, n], n):
+                    rng = np.random.default_rng([13, n, r, sign + 1, ldt])
+                    T = dev(host)
+                    V = dev(0.05 * rng.standard_normal((n + 2) * r))
+                    lg = dev(np.zeros(h.L.capi_dchud_log_bytes(n, r) // 8 + 3))
+                    info = C.c_int(-99)
+                    h.call("capi_dchud", sign, n, r, T.data_ptr() + 8 * off, ldt, c0, V.data_ptr(), n + 2, lg.data_ptr(), C.byref(info))
+                    tag = f"n{n} r{r} s{sign:+d} {store}"
+                    print(f"dchud {tag} info {info.value} T {sha(T)} V {sha(V)} log {sha(lg)}")
+                    ihost = triangles([14, n], n, 0.01)[0 if ldt == 0 else 1][1]
+                    Ti = dev(ihost)
+                    h.call("capi_dchud_inv", sign, n, r, Ti.data_ptr() + 8 * off, ldt, c0, lg.data_ptr(), 0, n)
+                    print(f"dchud_inv {tag} [0,{n}) Tinv {sha(Ti)}")
+                    Ti = dev(ihost)
+                    h1 = n // 2 + 1
+                    h.call("capi_dchud_inv", sign, n, r, Ti.data_ptr() + 8 * off, ldt, c0, lg.data_ptr(), 0, h1)
+                    h.call("capi_dchud_inv", sign, n, r, Ti.data_ptr() + 8 * off, ldt, c0, lg.data_ptr(), h1, n)
+                    print(f"dchud_inv {tag} [0,{h1})+[{h1},{n}) Tinv {sha(Ti)}")
+
+    # ---- capi_dsym_abs ----
+    for n in (300, 777):
+        for lda in (n, n + 3):
+            rng = np.random.default_rng([15, n, lda])
+            A = dev(rng.standard_normal(lda * n))                         # the lower triangle and the padding hold values: they take no part
+            for r in (5, 20):
+                rng = np.random.default_rng([16, n, lda, r])
+                X, B = dev(rng.standard_normal((n + 1) * r)), dev(rng.standard_normal((n + 2) * r))
+                tag = f"n{n} lda{lda} r{r}"
+                W, cm = out(rng, (n + 4) * r, 1), out(rng, r + 1, 1)
+                h.call("capi_dsym_abs", n, r, A.data_ptr(), lda, X.data_ptr(), n + 1, B.data_ptr(), n + 2, W.data_ptr(), n + 4, cm.data_ptr())
+                print(f"dsym_abs {tag} B W {sha(W)} colmax {sha(cm)}")
+                h.call("capi_dsym_abs", n, r, A.data_ptr(), lda, X.data_ptr(), n + 1, None, 0, W.data_ptr(), n + 4, cm.data_ptr())
+                print(f"dsym_abs {tag} no-B W {sha(W)} colmax {sha(cm)}")
+                h.call("capi_dsym_abs", n, r, A.data_ptr(), lda, X.data_ptr(), n + 1, B.data_ptr(), n + 2, None, 0, cm.data_ptr())
+                print(f"dsym_abs {tag} B no-W colmax {sha(cm)}")
+                h.call("capi_dsym_abs", n, r, A.data_ptr(), lda, X.data_ptr(), n + 1, None, 0, W.data_ptr(), n + 4, None)
+                print(f"dsym_abs {tag} no-B W-only W {sha(W)}")
     h.close()
     return 0
 
