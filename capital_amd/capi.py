@@ -50,6 +50,9 @@ _SIGS = {
     "capi_dcolnorm2": [_i64, _i64, _vp, _i64, _vp],
     "capi_dtri_rownorm2": [_int, _i64, _i64, _vp, _i64, _i64, _dbl, _vp],
     "capi_dtri_logdiag": [_i64, _vp, _i64, _i64, _vp],
+    "capi_dpoequ2": [_i64, _vp, _i64, _vp, _vp],
+    "capi_dsym_scale2": [_i64, _vp, _i64, _vp, _int],
+    "capi_drow_scale2": [_i64, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp],
     "capi_dlacn_block": [_int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, C.POINTER(_int)],
     "capi_dgesvj": [_i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, C.POINTER(_int)],
     "capi_dpstrf": [_i64, _vp, _i64, _dbl, _vp, C.POINTER(_int)],

@@ -67,6 +67,8 @@ def bind(D):
     D.capital_cholinv_quadratic_forms.argtypes = [_vp, _i64, _dp, _dp]
     D.capital_cholinv_logdet.argtypes = [_vp, _dp]
     D.capital_cholinv_inverse_diagonal.argtypes = [_vp, _dp]
+    D.capital_cholinv_equilibrate.argtypes = [_vp, _dbl, C.POINTER(_int), _dp, _dp, _dp]
+    D.capital_cholinv_unequilibrate.argtypes = [_vp]
     D.capital_cacqr_create.argtypes = [_i64, _i64] + [_int] * 8
     D.capital_cacqr_create.restype = _vp
     D.capital_cacqr_set_A.argtypes = [_vp, _dp]
@@ -168,14 +170,41 @@ class Cholinv:
         nloc, x, y, z, d, cc = _i64(), _int(), _int(), _int(), _int(), _int()
         _ck(self.D.capital_cholinv_dims(self.p, C.byref(nloc), C.byref(x), C.byref(y), C.byref(z), C.byref(d), C.byref(cc)), "dims")
         self.n, self.n_loc, self.x, self.y, self.z, self.d, self.c = n, nloc.value, x.value, y.value, z.value, d.value, cc.value
+        self._dscale = None
 
     def generate(self):
         _ck(self.D.capital_cholinv_generate(self.p), "generate")
+        self._dscale = None
 
     def set_A(self, A_local):
         a = np.asfortranarray(A_local, dtype=np.float64)
         assert a.shape == (self.n_loc, self.n_loc)
         _ck(self.D.capital_cholinv_set_A(self.p, a.ctypes.data_as(_dp)), "set_A")
+        self._dscale = None
+
+    def equilibrate(self, thresh=0.1):
+        """Power-of-two equilibration of a badly scaled SPD matrix (cholesky::cholinv::equilibrate, one rank; LAPACK's dpoequb + dlaqsy): with
+        d_j = 2^e_j, e_j = floor(ex_j / 2) for a_jj = f 2^ex_j, A's upper triangle becomes that of A_s = D^-1 A D^-1 (diagonal in [0.5, 2)) iff
+        scond = min d / max d < thresh, or amax = max a_jj lies outside [DBL_MIN / eps, eps / DBL_MIN]; thresh > 1 forces it.  Returns
+        (scaled, scond, amax).  scaled=True: factor() again -- it factors A_s -- and solve, solve_expert, update, apply, quadratic_forms, logdet and
+        inverse_diagonal then answer for the ORIGINAL matrix, bit for bit as without equilibration where nothing over- or underflows; rcond() is that of
+        A_s and ferr bounds the error in the scaled unknowns, ||D (x - x_true)||_inf / ||D x||_inf.  A(), R() and Rinv() show what lies on the device:
+        A_s and its factors.  scaled=False: nothing changed, valid factors stay valid.  Raises DriverError when a diagonal entry is not a positive
+        finite number (A is unchanged) and when A is already equilibrated."""
+        scaled, scond, amax = _int(0), _dbl(0.0), _dbl(0.0)
+        d = np.ones(self.n_loc)
+        _ck(self.D.capital_cholinv_equilibrate(self.p, float(thresh), C.byref(scaled), C.byref(scond), C.byref(amax), d.ctypes.data_as(_dp)), "equilibrate")
+        self._dscale = d if scaled.value else None
+        return bool(scaled.value), scond.value, amax.value
+
+    def scale(self):
+        """the scale factors in force, n powers of two: D's diagonal while A is equilibrated, ones otherwise"""
+        return np.ones(self.n_loc) if self._dscale is None else self._dscale.copy()
+
+    def unequilibrate(self):
+        """A's upper triangle <- that of D A_s D, every bit as before equilibrate() (cholesky::cholinv::unequilibrate); factor() again afterwards"""
+        _ck(self.D.capital_cholinv_unequilibrate(self.p), "unequilibrate")
+        self._dscale = None
 
     def factor(self):
         _ck(self.D.capital_cholinv_factor(self.p), "factor")

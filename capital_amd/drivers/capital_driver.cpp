@@ -55,6 +55,8 @@ struct cholinv_problem {
   virtual void quadratic_forms(int64_t r, const double* B_host, double* q_host) = 0;
   virtual void logdet(double* v) = 0;
   virtual void inverse_diagonal(double* d_host) = 0;
+  virtual void equilibrate(double thresh, int* scaled, double* scond, double* amax, double* dscale_host) = 0;
+  virtual void unequilibrate() = 0;
 };
 
 template <class Alg>
@@ -64,8 +66,9 @@ struct cholinv_impl : cholinv_problem {
   typename Alg::template info<T, U> pack;
   cholinv_impl(int64_t n, int c, int layout, int chunks, int complete_inv, int split, int bc_mult)
       : grid(capital::world(), (size_t)c, (size_t)layout, (size_t)chunks), A(n, n, grid.d, grid.d), pack(complete_inv, split, bc_mult, 'U') {}
-  void generate() override { A.distribute_symmetric(grid.x, grid.y, grid.d, grid.d, grid.rank / grid.c, true); }   // bench/cholesky/cholinv.cpp:40
-  void set_A(const double* host) override { A.from_host(host); }
+  // (a new matrix is not equilibrated, whatever the one before it was)
+  void generate() override { A.distribute_symmetric(grid.x, grid.y, grid.d, grid.d, grid.rank / grid.c, true); pack.equilibrated = false; }   // bench/cholesky/cholinv.cpp:40
+  void set_A(const double* host) override { A.from_host(host); pack.equilibrated = false; }
   void factor() override { Alg::factor(A, pack, grid); }
   double residual() override { return cholesky::validate<Alg>::residual(A, pack, grid); }
   void get(int which, double* host) override {
@@ -171,6 +174,20 @@ struct cholinv_impl : cholinv_problem {
     Alg::inverse_diagonal(pack, grid);
     std::memcpy(d_host, pack.inv_diag.data(), sizeof(double) * pack.inv_diag.size());
   }
+  // A <- D^-1 A D^-1 where dlaqsy's rule asks for it: *scaled, the scond and amax the call found, and (dscale_host may be NULL) the n scale factors in
+  // force afterwards: D's diagonal when it scaled, ones when it did not
+  void equilibrate(double thresh, int* scaled, double* scond, double* amax, double* dscale_host) override {
+    const bool did = Alg::equilibrate(A, pack, grid, thresh);
+    if (scaled) *scaled = did ? 1 : 0;
+    if (scond) *scond = pack.scond;
+    if (amax) *amax = pack.amax;
+    if (dscale_host) {
+      const size_t n = (size_t)A.num_rows_local();
+      if (did) std::memcpy(dscale_host, pack.dscale.data(), sizeof(double) * n);
+      else std::fill(dscale_host, dscale_host + n, 1.0);
+    }
+  }
+  void unequilibrate() override { Alg::unequilibrate(A, pack, grid); }
 };
 
 template <class SP, class IP>
@@ -416,6 +433,13 @@ int capital_cholinv_quadratic_forms(void* p, int64_t r, const double* B_host, do
 int capital_cholinv_logdet(void* p, double* v) { return guarded([&] { ((cholinv_problem*)p)->logdet(v); }); }
 // d_host[i] <- (A^-1)_ii, n results; -1 in TRSM mode, which has no inverse
 int capital_cholinv_inverse_diagonal(void* p, double* d_host) { return guarded([&] { ((cholinv_problem*)p)->inverse_diagonal(d_host); }); }
+// Badly scaled matrices (cholesky::cholinv::equilibrate / unequilibrate; one rank): A <- D^-1 A D^-1 with D = diag(2^e_j) from A's diagonal, iff scond < thresh
+// or amax lies outside [SMALL, LARGE] (dlaqsy's rule; thresh > 1 forces it).  *scaled: 1 when it scaled -- capital_cholinv_factor then factors the scaled
+// matrix and every operation on the factors answers for the original one -- 0 when nothing changed.  dscale_host_or_null: n doubles.
+int capital_cholinv_equilibrate(void* p, double thresh, int* scaled, double* scond, double* amax, double* dscale_host_or_null) {
+  return guarded([&] { ((cholinv_problem*)p)->equilibrate(thresh, scaled, scond, amax, dscale_host_or_null); });
+}
+int capital_cholinv_unequilibrate(void* p) { return guarded([&] { ((cholinv_problem*)p)->unequilibrate(); }); }
 int capital_cholinv_destroy(void* p) { return guarded([&] { capital::sync(); delete (cholinv_problem*)p; }); }
 
 void* capital_cacqr_create(int64_t m, int64_t n, int c, int variant, int layout, int num_chunks, int complete_inv, int split, int bc_mult, int serialize_) {

@@ -15,6 +15,8 @@
 #ifndef CAPITAL_CHOLESKY_CHOLINV_H_
 #define CAPITAL_CHOLESKY_CHOLINV_H_
 
+#include <cfloat>
+
 #include "./../../alg.h"
 #include "./../../matmult/summa/summa.h"
 #include "./policy.h"
@@ -45,6 +47,10 @@
 #pragma weak capi_dtri_rownorm2
 #pragma weak capi_dtri_logdiag
 #pragma weak capi_dcolnorm2
+// .. and the power-of-two equilibration: without them equilibrate() refuses and everything else runs as before
+#pragma weak capi_dpoequ2
+#pragma weak capi_dsym_scale2
+#pragma weak capi_drow_scale2
 
 namespace cholesky {
 
@@ -134,6 +140,14 @@ public:
     std::vector<int> pivl;
     int64_t pivot_rank = 0;
     double resid_trace = 0.0, pivot_thresh = 0.0;
+    // equilibrate(): `equilibrated` -- A holds A_s = D^-1 A0 D^-1 and every operation on the factors answers for the original A0 = D A_s D; Dscale
+    // (device, n doubles) / dscale (host): D's diagonal, powers of two 2^e_j; equil_exponents: the sum of the e_j (log_determinant()); scond = min d /
+    // max d and amax = max a_jj as the last equilibrate() found them, whether or not it scaled
+    bool equilibrated = false;
+    matrix<ScalarType, DimensionType, rect> Dscale;
+    std::vector<double> dscale;
+    int64_t equil_exponents = 0;
+    double scond = 1.0, amax = 0.0;
   };
 
   template <typename MatrixType, typename ArgType, typename CommType>
@@ -246,6 +260,85 @@ public:
     args.factored = true;
   }
 
+  // ---- a badly scaled A (a covariance in mixed units, A0 = D0 C D0 with C well conditioned and D0 spanning many decades): LAPACK dposvx's
+  // equilibration (dpoequb + dlaqsy), which the reference's cholinv lacks.  ONE rank.
+  // equilibrate(): capi_dpoequ2 reads the diagonal and gives d_j = 2^e_j, e_j = floor(ex_j / 2) for a_jj = f 2^ex_j (the rule of
+  // capi_dgram_equilibrate_shift, at any order), scond = min d / max d and amax = max a_jj (args.scond, args.amax).  A is scaled iff scond < thresh, or
+  // amax < SMALL, or amax > LARGE with SMALL = DBL_MIN / DBL_EPSILON and LARGE = 1 / SMALL (dlaqsy's rule; thresh > 1 forces it): A's upper triangle
+  // becomes that of A_s = D^-1 A D^-1 in place (capi_dsym_scale2: one pass at the rate of a copy), whose diagonal lies in [0.5, 2);
+  // args.equilibrated = true, args.factored = false -- factor() then factors the A that lies there, A_s -- and true is returned.  Otherwise nothing
+  // changes (valid factors stay valid) and false is returned.  A diagonal entry that is zero, negative, NaN or Inf: std::domain_error naming it, A
+  // untouched.  Calling it while equilibrated: std::logic_error.
+  // What it buys, and what not: the factors are homogeneous (R_s D is the Cholesky factor of A0, bit for bit where nothing over- or underflows), so no
+  // bit of a solution changes; what changes is what rcond and ferr MEAN -- the condition and the error of the scaled problem, which is what governs
+  // the accuracy -- and a matrix whose entries sit near the ends of the fp64 range is moved into its middle.
+  // While args.equilibrated is set every operation answers for the ORIGINAL matrix A0 = D A_s D, whose factor is R0 = R_s D, through exact row scalings
+  // (capi_drow_scale2): solve() runs on B_s = D^-1 B and returns X = D^-1 X_s, its residual norms are ||b - A0 x||_2 = ||D rho_s||_2; condition():
+  // anorm1 and rcond of A_s, as dposvx defines them after equilibration; error_bounds() runs on (A_s, B_s, X_s = D X): berr is scale-invariant, ferr
+  // bounds the error in the SCALED unknowns, ||D (x - x_true)||_inf / ||D x||_inf (it is not divided by scond as dposvx does: that turns a bound of 1e-10
+  // into 1e5 on a matrix graded over 16 decades); update(V) uses D^-1 V; apply(): R: R_s (D b), Rt: D (R_s^T b), Rinv: D^-1 (R_s^-1 b), RinvT:
+  // R_s^-T (D^-1 b); quadratic_forms() uses D^-1 B; log_determinant() adds 2 ln 2 sum e_j (the sum taken as an integer); inverse_diagonal() scales entry
+  // i by 2^(-2 e_i); factor_pivoted() refuses (std::logic_error: its stopping rule on the scaled matrix is a design of its own).  construct_R,
+  // construct_Rinv and the validators keep referring to the matrix that lies in A: R_s, R_s^-1 and A_s.
+  // Memory, of args.ops: four doubles.
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static bool equilibrate(MatrixType& A, ArgType& args, CommType&& CommInfo, double thresh = 0.1) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::equilibrate takes a rect-structured A");
+    if (CommInfo.size > 1) throw std::logic_error("cholinv::equilibrate is built for one rank: on a grid the matrix is element-cyclic");
+    require_equil_abi();
+    if (args.equilibrated) throw std::logic_error("cholinv::equilibrate: A is already equilibrated: unequilibrate() first");
+    const int64_t n = A.num_rows_local();
+    if (A.num_columns_local() != n || !(thresh == thresh)) throw std::invalid_argument("cholinv::equilibrate: A n x n, thresh not NaN");
+    if (n == 0) return false;
+    CRITTER_START(CI::equilibrate);
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    args.Dscale._register_(1, n, 1, 1);
+    double rec[4];
+    {
+      ops_scope ops(args.ops, 0, n, 4);
+      double* const drec = ops.piece(4);
+      CAPITAL_CHECK(capi_dpoequ2(h, n, A.data(), n, args.Dscale.data(), drec));
+      CAPITAL_CHECK(capi_memcpy_d2h(h, rec, drec, sizeof(rec)));
+    }
+    bool scale = false;
+    if (rec[3] == 0.0) {
+      args.scond = rec[0]; args.amax = rec[1];
+      const double SMALL = DBL_MIN / DBL_EPSILON, LARGE = 1.0 / SMALL;
+      scale = args.scond < thresh || args.amax < SMALL || args.amax > LARGE || thresh > 1.0;
+      if (scale) {
+        CAPITAL_CHECK(capi_dsym_scale2(h, n, A.data(), n, args.Dscale.data(), 1));
+        args.dscale = args.Dscale.to_host();
+        args.equil_exponents = 0;
+        for (double d : args.dscale) { int e; (void)std::frexp(d, &e); args.equil_exponents += e - 1; }
+        args.equilibrated = true;
+        args.factored = false;
+      }
+    }
+    CRITTER_STOP(CI::equilibrate);
+    if (rec[3] != 0.0)
+      throw std::domain_error("cholinv::equilibrate: diagonal entry " + std::to_string((int64_t)rec[3]) + " (1-based) is zero, negative, NaN or Inf: "
+                              "the matrix is not positive definite; A is unchanged");
+    return scale;
+  }
+
+  // A's upper triangle <- that of D A_s D = A0, every bit as before equilibrate() (the scale factors are powers of two); args.equilibrated = false,
+  // args.factored = false: the resident factors are those of A_s.  std::logic_error when A is not equilibrated.
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void unequilibrate(MatrixType& A, ArgType& args, CommType&& CommInfo) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::unequilibrate takes a rect-structured A");
+    if (CommInfo.size > 1) throw std::logic_error("cholinv::unequilibrate is built for one rank: on a grid the matrix is element-cyclic");
+    require_equil_abi();
+    if (!args.equilibrated) throw std::logic_error("cholinv::unequilibrate: A is not equilibrated");
+    const int64_t n = A.num_rows_local();
+    if (A.num_columns_local() != n || (int64_t)args.dscale.size() != n) throw std::invalid_argument("cholinv::unequilibrate: A must be the equilibrated matrix");
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    CAPITAL_CHECK(capi_dsym_scale2(h, n, A.data(), n, args.Dscale.data(), -1));
+    args.equilibrated = false;
+    args.factored = false;
+  }
+
   // A X = B on the factors factor(A, args, CommInfo) left, ONE rank: args.X (n x r) and, with `residual`, args.solve_residual_norms[j] =
   // ||b_j - A x_j||_2.  B: matrix<double, int64_t, rect>(r, n, 1, 1).  The inverse is applied by products, CAPI_TS_MAX_RHS columns at a time
   // (capi_dtrmm_thin: the factor is read once per product, packed or not, no copy of it is made):
@@ -259,6 +352,9 @@ public:
   // norms read A's UPPER triangle alone, as factor() does (capi_dresid_sym: a tile of the triangle serves the lines of its rows and, transposed,
   // of its columns): what lies below the diagonal is never used, in any mode.  (With a C-ABI library that lacks capi_dresid_sym both passes fall back to
   // capi_dresid_ts over all of A, which reads both triangles.)  refine == 0 and residual == false do not touch A.
+  // After equilibrate() (args.equilibrated; A holds A_s = D^-1 A0 D^-1): the loop runs on B_s = D^-1 B and X = D^-1 X_s is returned, the same bytes as
+  // without equilibration where nothing over- or underflows; the norms are ||b - A0 x||_2 = ||D rho_s||_2.  One n x CAPI_TS_MAX_RHS block of args.ops
+  // more, three with `residual`.
   template <typename MatrixType, typename ArgType, typename CommType>
   static void solve(const MatrixType& A, const MatrixType& B, ArgType& args, CommType&& CommInfo, int refine = 1, bool residual = true) {
     static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::solve takes rect-structured A and B");
@@ -272,10 +368,17 @@ public:
     CAPITAL_CHECK(capi_stream_select(h, 0));
     const int64_t W = CAPI_TS_MAX_RHS;
     util::resize_columns(args.X, r, n);
-    ops_scope ops(args.ops, ap.work_blocks + (refine > 0 ? 2 : 0), n, 0);
+    // equilibrated: the loop below runs on B_s = D^-1 B (bs) and leaves X_s, which becomes X = D^-1 X_s in place; the residual pass forms X_s = D X
+    // again (xs) and rho_s (rs) and takes the norms of D rho_s
+    const bool eq = args.equilibrated;
+    const double* const D = eq ? args.Dscale.data() : nullptr;
+    ops_scope ops(args.ops, ap.work_blocks + (refine > 0 ? 2 : 0) + (eq ? (residual ? 3 : 1) : 0), n, 0);
     take_applier_work(ap, ops);
     double* const rho = refine > 0 ? ops.block() : nullptr;
     double* const corr = refine > 0 ? ops.block() : nullptr;
+    double* const bs = eq ? ops.block() : nullptr;
+    double* const xs = eq && residual ? ops.block() : nullptr;
+    double* const rs = eq && residual ? ops.block() : nullptr;
     auto apply = [&](const double* Bi, double* Xo, int64_t rb) { apply_inverse(ap, Bi, Xo, rb); };
     // Ro (or nothing) <- Bi - A Xi, norm2 (or nothing) <- its squared column norms, from A's upper triangle
     auto resid = [&](int64_t rb, const double* Xi, const double* Bi, double* Ro, double* norm2) {
@@ -286,17 +389,23 @@ public:
       const int64_t rb = std::min(W, r - j);
       double* Xj = args.X.data() + j * n;
       const double* Bj = B.data() + j * n;
+      if (eq && n > 0) { CAPITAL_CHECK(capi_drow_scale2(h, n, rb, D, -1, Bj, n, bs, n, nullptr)); Bj = bs; }
       apply(Bj, Xj, rb);
       for (int it = 0; it < refine; ++it) {
         resid(rb, Xj, Bj, rho, nullptr);
         apply(rho, corr, rb);
         CAPITAL_CHECK(capi_dgeadd(h, 0, n, rb, 1.0, corr, n, 1.0, Xj, n));
       }
+      if (eq && n > 0) CAPITAL_CHECK(capi_drow_scale2(h, n, rb, D, -1, Xj, n, Xj, n, nullptr));
     }
     args.solve_residual_norms.clear();
     if (residual)
       args.solve_residual_norms = util::residual_norms(args.SolveNorm2, r, nullptr, [&](int64_t j, int64_t rb, double* norm2) {
-        resid(rb, args.X.data() + j * n, B.data() + j * n, nullptr, norm2);
+        if (!eq || n == 0) { resid(rb, args.X.data() + j * n, B.data() + j * n, nullptr, norm2); return; }
+        CAPITAL_CHECK(capi_drow_scale2(h, n, rb, D, -1, B.data() + j * n, n, bs, n, nullptr));
+        CAPITAL_CHECK(capi_drow_scale2(h, n, rb, D, 1, args.X.data() + j * n, n, xs, n, nullptr));
+        resid(rb, xs, bs, rs, nullptr);
+        CAPITAL_CHECK(capi_drow_scale2(h, n, rb, D, 1, rs, n, rs, n, norm2));
       });
     CRITTER_STOP(CI::solve);
   }
@@ -366,15 +475,23 @@ public:
     capi_handle_t h = capital::handle();
     CAPITAL_CHECK(capi_stream_select(h, 0));
     const int64_t W = CAPI_TS_MAX_RHS;
-    ops_scope ops(args.ops, ap.work_blocks + 4, n, estimator::tail(n));
+    // equilibrated: everything below runs on the scaled problem (A_s, B_s = D^-1 B, X_s = D X)
+    const bool eq = args.equilibrated;
+    ops_scope ops(args.ops, ap.work_blocks + 4 + (eq ? 2 : 0), n, estimator::tail(n));
     take_applier_work(ap, ops);
     double *const rho = ops.block(), *const wt = ops.block();
+    double *const bs = eq ? ops.block() : nullptr, *const xs = eq ? ops.block() : nullptr;
     const estimator es(ops, n);
     double* const small = es.small;
     for (int64_t j = 0; j < r; j += W) {
       const int64_t rb = std::min(W, r - j);
       const double* Xj = args.X.data() + j * n;
       const double* Bj = B.data() + j * n;
+      if (eq) {
+        CAPITAL_CHECK(capi_drow_scale2(h, n, rb, args.Dscale.data(), -1, Bj, n, bs, n, nullptr));
+        CAPITAL_CHECK(capi_drow_scale2(h, n, rb, args.Dscale.data(), 1, Xj, n, xs, n, nullptr));
+        Bj = bs; Xj = xs;
+      }
       CAPITAL_CHECK(capi_dresid_sym(h, n, rb, A.data(), n, Xj, n, Bj, n, rho, n, nullptr));
       CAPITAL_CHECK(capi_dsym_abs(h, n, rb, A.data(), n, Xj, n, Bj, n, wt, n, nullptr));
       CAPITAL_CHECK(capi_dberr(h, n, rb, rho, n, wt, n, small));                               // berr; wt becomes the forward bound's weights
@@ -424,13 +541,21 @@ public:
     const image Iw = inverse ? pick_image(args.Rinv, args.Rinvfull, n, image_use::in_place, "cholinv::update") : image();
     const typename image::block Rb = Rw.at(0, 0), Ib = Iw.at(0, 0);
     const int64_t log_count = (int64_t)((capi_dchud_log_bytes(n, W) + 7) / 8);
-    ops_scope ops(args.ops, 1, n, even(log_count));
+    // equilibrated: A_s + sign (D^-1 V) (D^-1 V)^T = D^-1 (A0 + sign V V^T) D^-1: the whole call runs on Vs = D^-1 V
+    const bool eq = args.equilibrated;
+    ops_scope ops(args.ops, 1, n, even(log_count) + (eq ? even(n * r) : 0));
     double *const v = ops.block(), *const log = ops.piece(log_count);
+    const double* Vp = V.data();
+    if (eq) {
+      double* const Vs = ops.piece(n * r);
+      CAPITAL_CHECK(capi_drow_scale2(h, n, r, args.Dscale.data(), -1, V.data(), n, Vs, n, nullptr));
+      Vp = Vs;
+    }
     int info = 0;
     int64_t bad_block = 0;
     for (int64_t j = 0; j < r && info == 0; j += W) {
       const int64_t rb = std::min(W, r - j);
-      CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, V.data() + j * n, n, v, n));
+      CAPITAL_CHECK(capi_dlacpy(h, 0, n, rb, Vp + j * n, n, v, n));
       CAPITAL_CHECK(capi_dchud(h, sign, n, rb, Rb.p, Rb.ldt, Rb.col0, v, n, log, &info));
       if (info != 0) { bad_block = j; break; }
       if (!inverse) continue;
@@ -445,7 +570,7 @@ public:
       // a working image took the steps: the packed factor beside it follows
       if (Rw.working) serialize<uppertri, uppertri>::invoke(args.Rfull, args.R, 0, n, 0, n, 0, n, 0, n);
       if (Iw.working) serialize<uppertri, uppertri>::invoke(args.Rinvfull, args.Rinv, 0, n, 0, n, 0, n, 0, n);
-      CAPITAL_CHECK(capi_dsyrk(h, CAPI_UPPER, CAPI_NOTRANS, n, r, (double)sign, V.data(), n, 1.0, A.data(), n));
+      CAPITAL_CHECK(capi_dsyrk(h, CAPI_UPPER, CAPI_NOTRANS, n, r, (double)sign, Vp, n, 1.0, A.data(), n));
     } else {
       args.factored = false;
       args.update_info = info;
@@ -485,13 +610,21 @@ public:
     CAPITAL_CHECK(capi_stream_select(h, 0));
     const int64_t W = CAPI_TS_MAX_RHS;
     util::resize_columns(args.Y, r, n);
-    ops_scope ops(args.ops, inverse ? half_work_blocks(ap) : 0, n, 0);
+    // equilibrated (R0 = R_s D): R and R^-T scale the block that goes in (by D and D^-1, into a work block), R^T and R^-1 the one that comes out (by D
+    // and D^-1, in place)
+    const bool eq = args.equilibrated, scale_in = eq && (op == factor_op::R || op == factor_op::RinvT), scale_out = eq && !scale_in;
+    const int dsign = (op == factor_op::R || op == factor_op::Rt) ? 1 : -1;
+    ops_scope ops(args.ops, (inverse ? half_work_blocks(ap) : 0) + (scale_in ? 1 : 0), n, 0);
     if (inverse) take_half_work(ap, ops);
+    double* const bs = scale_in ? ops.block() : nullptr;
     const typename image::block T = Rw.at(0, 0);
     for (int64_t j = 0; j < r && n > 0; j += W) {
       const int64_t rb = std::min(W, r - j);
-      if (inverse) apply_half(ap, trans, B.data() + j * n, args.Y.data() + j * n, rb);
-      else CAPITAL_CHECK(capi_dtrmm_thin(h, CAPI_UPPERTRI, trans, n, n, rb, 1.0, T.p, T.ldt, T.col0, B.data() + j * n, n, 0.0, args.Y.data() + j * n, n));
+      const double* Bj = B.data() + j * n;
+      if (scale_in) { CAPITAL_CHECK(capi_drow_scale2(h, n, rb, args.Dscale.data(), dsign, Bj, n, bs, n, nullptr)); Bj = bs; }
+      if (inverse) apply_half(ap, trans, Bj, args.Y.data() + j * n, rb);
+      else CAPITAL_CHECK(capi_dtrmm_thin(h, CAPI_UPPERTRI, trans, n, n, rb, 1.0, T.p, T.ldt, T.col0, Bj, n, 0.0, args.Y.data() + j * n, n));
+      if (scale_out) CAPITAL_CHECK(capi_drow_scale2(h, n, rb, args.Dscale.data(), dsign, args.Y.data() + j * n, n, args.Y.data() + j * n, n, nullptr));
     }
     CRITTER_STOP(CI::apply);
   }
@@ -514,12 +647,17 @@ public:
     const int64_t W = CAPI_TS_MAX_RHS;
     util::resize_columns(args.Quad, r, 1);
     {
-      ops_scope ops(args.ops, half_work_blocks(ap) + 1, n, 0);
+      // equilibrated: b^T A0^-1 b = ||R_s^-T (D^-1 b)||^2
+      const bool eq = args.equilibrated;
+      ops_scope ops(args.ops, half_work_blocks(ap) + 1 + (eq ? 1 : 0), n, 0);
       take_half_work(ap, ops);
       double* const y = ops.block();
+      double* const bs = eq ? ops.block() : nullptr;
       for (int64_t j = 0; j < r; j += W) {
         const int64_t rb = std::min(W, r - j);
-        if (n > 0) apply_half(ap, CAPI_TRANS, B.data() + j * n, y, rb);
+        const double* Bj = B.data() + j * n;
+        if (eq && n > 0) { CAPITAL_CHECK(capi_drow_scale2(h, n, rb, args.Dscale.data(), -1, Bj, n, bs, n, nullptr)); Bj = bs; }
+        if (n > 0) apply_half(ap, CAPI_TRANS, Bj, y, rb);
         CAPITAL_CHECK(capi_dcolnorm2(h, n, rb, y, std::max<int64_t>(n, 1), args.Quad.data() + j));
       }
       args.quad = args.Quad.to_host();
@@ -546,6 +684,8 @@ public:
       CAPITAL_CHECK(capi_memcpy_d2h(h, &half, out, sizeof(double)));
     }
     args.logdet = 2.0 * half;
+    // equilibrated: det A0 = det(D)^2 det A_s, and det D = 2^(sum e_j), the sum an integer
+    if (args.equilibrated) args.logdet += 2.0 * 0.6931471805599453094 * (double)args.equil_exponents;
     CRITTER_STOP(CI::log_determinant);
   }
 
@@ -613,6 +753,9 @@ public:
       CAPITAL_CHECK(capi_dtrmm(h, CAPI_RIGHT, CAPI_UPPER, CAPI_NOTRANS, CAPI_NONUNIT, h1, h2, -1.0, I22, ld22, I12, h1));
       rownorm2(CAPI_RECT, h1, h2, typename image::block{I12, h1, 0}, 1.0, out);
     }
+    // equilibrated: A0^-1 = D^-1 A_s^-1 D^-1: entry i takes 2^(-2 e_i), in two exact steps of 2^-e_i (the first result is a normal number)
+    if (args.equilibrated && n > 0)
+      for (int k = 0; k < 2; ++k) CAPITAL_CHECK(capi_drow_scale2(h, n, 1, args.Dscale.data(), -1, out, n, out, n, nullptr));
     args.inv_diag.resize((size_t)n);
     if (n > 0) CAPITAL_CHECK(capi_memcpy_d2h(h, args.inv_diag.data(), out, sizeof(double) * (size_t)n));
     CRITTER_STOP(CI::inverse_diagonal);
@@ -631,6 +774,8 @@ public:
     static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::factor_pivoted takes a rect-structured input block");
     if (CommInfo.size > 1) throw std::logic_error("cholinv::factor_pivoted is built for one rank: on a grid the matrix is element-cyclic");
     if (!&capi_dpchol || !&capi_dpchol_thresh) throw std::logic_error("cholinv: this C-ABI library has no capi_dpchol: no pivoted factorization");
+    if (args.equilibrated)
+      throw std::logic_error("cholinv::factor_pivoted: A is equilibrated (its stopping rule on the scaled matrix is a design of its own): unequilibrate() first");
     const int64_t n = A.num_rows_local();
     const int64_t cap = std::min<int64_t>(n, CAPI_PCHOL_MAX_RANK), kmax = args.pivot_max_rank == 0 ? cap : args.pivot_max_rank;
     if (n < 1 || A.num_columns_local() != n || kmax < 1 || kmax > cap || !(args.pivot_rtol >= 0.0))
@@ -844,7 +989,8 @@ private:
   // each is 256 n bytes, so every one lies at a multiple of 256 bytes from the arena's base -- no operand is less aligned than in an allocation of its
   // own -- and the pieces follow them.  Nothing is zeroed and nothing needs to be: no kernel of these operations reads work that it or a kernel before it
   // in the same call has not written (beta == 0 products do not read C; capi_dresid_sym, capi_dsym_abs and capi_dlacn_block(init) only store to their
-  // outputs; capi_dchud reads r columns of V and capi_dchud_inv only logged steps; the rows of w2 above h1 are never addressed).  On every exit,
+  // outputs; capi_dchud reads r columns of V and capi_dchud_inv only logged steps; the rows of w2 above h1 are never addressed; the blocks that an
+  // equilibrated operation adds -- B_s, X_s, rho_s, D^-1 V -- are each written whole by capi_drow_scale2 or capi_dresid_sym before anything reads them).  On every exit,
   // exceptions included, FlushIntermediates drains the stream and releases the arena (a failure of that drain shows at the next checked call);
   // SaveIntermediates keeps the arena at its high-water mark.
   struct ops_scope {
@@ -954,6 +1100,10 @@ private:
       throw std::logic_error(who + ": factor() has not run or did not succeed: there are no valid factors to solve with");
     if (args.factored_trsm != args.solve_with_trsm)
       throw std::logic_error(who + ": solve_with_trsm was changed after factor(): the resident factors are those of the other mode; factor() again");
+  }
+  static void require_equil_abi() {
+    if (!&capi_dpoequ2 || !&capi_dsym_scale2 || !&capi_drow_scale2)
+      throw std::logic_error("cholinv: this C-ABI library has no capi_dpoequ2 / capi_dsym_scale2 / capi_drow_scale2: no equilibration");
   }
   static void require_bounds_abi() {
     if (!&capi_dsym_abs || !&capi_dberr || !&capi_dcolamax || !&capi_dlacn_block || !&capi_dlacn_state_bytes || !&capi_dresid_sym)

@@ -256,6 +256,31 @@ int capi_dtri_rownorm2(capi_handle_t h, int shape, int64_t m, int64_t n, const d
  * sign check: a non-positive or NaN diagonal entry gives -Inf or NaN in the sum.  n == 0: 0.  One workgroup; a thread adds the entries tid, tid + 256,
  * .., and the 256 sums meet pairwise in a fixed order (bit-identical runs).  No workspace. */
 int capi_dtri_logdiag(capi_handle_t h, int64_t n, const double* T, int64_t ldt, int64_t col0, double* out);
+/* ---- power-of-two equilibration of a badly scaled SPD matrix (cholesky::cholinv::equilibrate; LAPACK's dpoequb + dlaqsy).  Not in the reference:
+ * cholinv.hpp stops at R and R^-1.  The three calls share these conventions: DEVICE pointers, column-major; a null handle returns -1 before any device
+ * call; bad arguments return CAPI_EINVAL before any launch, nothing is touched; a size of 0 is a no-op; no atomics, sums and maxima in one fixed order
+ * (bit-identical runs).  The scale factors are powers of two -- the rule of capi_dgram_equilibrate_shift and capi_dtri_rescale, at any order -- so
+ * every operation is exact where nothing over- or underflows, and reversible bit for bit. ----
+ * capi_dpoequ2: the scale factors of A from its diagonal.  Not in the reference: cholinv.hpp stops at R and R^-1.  Only the n diagonal entries of the
+ * column-major A (lda >= n) are read.  With a_jj = f 2^ex_j, f in [0.5, 1) (the exponent is taken from the bits, subnormals included; no log, no
+ * sqrt): e_j = floor(ex_j / 2) and dscale[j] (n doubles) <- 2^e_j, always a normal number (-537 <= e_j <= 512); the diagonal of D^-1 A D^-1 then lies in
+ * [0.5, 2).  rec (4 doubles): rec[0] = scond = min dscale / max dscale, rec[1] = amax = max a_jj, rec[2] = min a_jj, rec[3] = 0 -- or rec[3] = j + 1
+ * for the FIRST j whose a_jj is zero, negative, NaN or Inf: then dscale is all ones, rec[0] = 1 and rec[1] = rec[2] = 0.  rec[3] is a word of its own,
+ * not the handle's potrf info word (capi_get_info).  One workgroup.  No workspace. */
+int capi_dpoequ2(capi_handle_t h, int64_t n, const double* A, int64_t lda, double* dscale, double* rec);
+/* capi_dsym_scale2: a_ij <- ldexp(a_ij, -sign (e_i + e_j)) IN PLACE on the upper triangle of A, diagonal included: sign = +1 gives A_s = D^-1 A D^-1,
+ * sign = -1 undoes it (anything else: CAPI_EINVAL).  Not in the reference: cholinv.hpp stops at R and R^-1.  e_i is the exponent field of dscale[i]
+ * (capi_dpoequ2's output: normal powers of two).  One exponent addition per element, never two multiplications: no intermediate can overflow; zero, Inf
+ * and NaN pass through unchanged, a result below the normal range is rounded once.  Nothing below the diagonal and no padding row (n .. lda - 1) is
+ * read into a result or changes a bit: it may hold NaN.  Any lda >= n; 16-byte accesses where A is 16-byte aligned and lda is even, 8-byte ones
+ * otherwise.  Only the 512 x 64 tiles that touch the triangle are launched; the tiles that the diagonal or the edge crosses select after loading.  The
+ * triangle is read and written once: the call is bound by that stream.  No workspace. */
+int capi_dsym_scale2(capi_handle_t h, int64_t n, double* A, int64_t lda, const double* dscale, int sign);
+/* capi_drow_scale2: Y(i, j) <- ldexp(X(i, j), sign e_i) for an m x r block, any r >= 1: Y = D X (sign = +1) or D^-1 X (sign = -1; anything else:
+ * CAPI_EINVAL), e_i as in capi_dsym_scale2.  Not in the reference: cholinv.hpp stops at R and R^-1.  ldx, ldy >= m; Y == X (with ldy == ldx) is allowed.
+ * norm2: NULL, or r doubles that receive the squared column norms of Y (a NaN showing; one workgroup per column, one fixed order of the sum, as
+ * capi_dcolnorm2); with NULL nothing but Y is written.  m == 0 or r == 0: nothing happens.  No workspace. */
+int capi_drow_scale2(capi_handle_t h, int64_t m, int64_t r, const double* dscale, int sign, const double* X, int64_t ldx, double* Y, int64_t ldy, double* norm2);
 /* capi_dlacn_block: the Hager-Higham estimator of a 1-norm (LAPACK dlacn2, Higham's refinements included) for r operators at once, by reverse
  * communication.  Not in the reference: cholinv.hpp stops at R and R^-1.  Column j estimates the 1-norm of diag(Wt(:, j)) Z -- which is
  * || Z diag(Wt(:, j)) ||_inf, dporfs's bound on || |Z| w ||_inf -- for a SYMMETRIC operator Z that the caller applies (cholinv: Z = A^-1);
