@@ -59,6 +59,9 @@ _SIGS = {
     "capi_drow_scatter": [_int, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64],
     "capi_dpchol": [_i64, _vp, _i64, _dbl, _i64, _vp, _i64, _vp, _vp, C.POINTER(_int), C.POINTER(_dbl)],
     "capi_dpchol_thresh": [_i64, _vp, _i64, _dbl, C.POINTER(_dbl)],
+    "capi_dlr_diag": [_i64, _dbl, _vp, _vp, _vp, _vp],
+    "capi_drow_pow": [_i64, _i64, _dbl, _vp, _dbl, _vp, _i64, _dbl, _vp, _i64, _vp],
+    "capi_ddiag_add": [_i64, _dbl, _vp, _i64],
     "capi_get_info": [C.POINTER(_int)],
     "capi_reset_info": [],
     "capi_serialize": [_int, _int, _vp, _i64, _i64, _vp, _i64, _i64] + [_i64] * 8,

@@ -69,6 +69,9 @@ def bind(D):
     D.capital_cholinv_inverse_diagonal.argtypes = [_vp, _dp]
     D.capital_cholinv_equilibrate.argtypes = [_vp, _dbl, C.POINTER(_int), _dp, _dp, _dp]
     D.capital_cholinv_unequilibrate.argtypes = [_vp]
+    D.capital_cholinv_lowrank_prepare.argtypes = [_vp, _dbl, _dp, _int, _dp, _dp]
+    D.capital_cholinv_lowrank_solve.argtypes = [_vp, _i64, _dp, _dp, _dp]
+    D.capital_cholinv_lowrank_quadratic_forms.argtypes = [_vp, _i64, _dp, _dp]
     D.capital_cacqr_create.argtypes = [_i64, _i64] + [_int] * 8
     D.capital_cacqr_create.restype = _vp
     D.capital_cacqr_set_A.argtypes = [_vp, _dp]
@@ -328,6 +331,7 @@ class Cholinv:
         DriverError at rank 0 (A is zero or not finite)."""
         rk, tr, th = _i64(0), _dbl(0.0), _dbl(0.0)
         self.pivot_rank = 0
+        self._lowrank = None       # (what lowrank_prepare() left belonged to the factor before this one)
         _ck(self.D.capital_cholinv_factor_pivoted(self.p, float(rtol), 0 if max_rank is None else int(max_rank), C.byref(rk), C.byref(tr), C.byref(th)),
             "factor_pivoted")
         self.pivot_rank = rk.value
@@ -354,6 +358,55 @@ class Cholinv:
     def schur_diagonal(self):
         """diag(A - L L^T) as factor_pivoted() carried it: the remaining Schur diagonal of the rows not chosen, 0 for the chosen ones"""
         return self._get_pivoted("d")
+
+    def lowrank_prepare(self, shift=0.0, diag=None, schur=False):
+        """Prepare solves with M = L L^T + D on the L of the last factor_pivoted() (cholesky::cholinv::lowrank_prepare, one rank), D the positive
+        diagonal d = shift + diag + (schur: schur_diagonal()): shift alone is Nystroem / subset-of-regressors regression with noise sigma^2 = shift,
+        schur=True adds diag(A - L L^T) and gives FITC.  diag: None or n values.  Forms and factors the rank x rank matrix C = I + L^T D^-1 L in
+        O(n rank^2); a uniform d (diag=None, schur=False) uses G = L^T L, which is kept, so that a sweep over shift on one factor pays the pass over L
+        once.  Returns {"logdet": log det M, "cnorm1": ||C||_1, "rank": rank}.  The Woodbury form is not backward stable: lowrank_solve,
+        lowrank_quadratic_forms and logdet carry errors of about cnorm1 * 2^-53, whatever kappa(C) is.  Neither A nor the factors of factor() are
+        touched.  Raises DriverError without a successful factor_pivoted(), for a shift that is negative or not finite, a diag of another length, and
+        when some d_i is not a finite number > 0 (a chosen row has Schur diagonal 0, so schur=True needs shift > 0); after a prepare that the device
+        layer refused lowrank_solve refuses until one succeeds, and after a new factor_pivoted() as well."""
+        self._lowrank = None
+        dv = None
+        if diag is not None:
+            dv = np.ascontiguousarray(diag, dtype=np.float64)
+            if dv.shape != (self.n,):
+                raise DriverError(f"Cholinv.lowrank_prepare: diag must have {self.n} entries, got shape {dv.shape}")
+        ld, cn = _dbl(0.0), _dbl(0.0)
+        _ck(self.D.capital_cholinv_lowrank_prepare(self.p, float(shift), dv.ctypes.data_as(_dp) if dv is not None else None, int(bool(schur)),
+                                                   C.byref(ld), C.byref(cn)), "lowrank_prepare")
+        self._lowrank = {"logdet": ld.value, "cnorm1": cn.value, "rank": getattr(self, "pivot_rank", 0)}
+        return dict(self._lowrank)
+
+    def lowrank_solve(self, B, residual=True):
+        """X = M^-1 B with the M = L L^T + D of the last lowrank_prepare() (cholesky::cholinv::lowrank_solve, one rank): X = D^-1 (B - L T),
+        T = C^-1 (L^T (D^-1 B)), in blocks of 32 columns; L is read twice per block as it lies, the rank x rank substitutions are capi_dtrsm_thin's.
+        B: n x r.  Returns (X, resnorms): resnorms[j] = ||b_j - M x_j||_2 with M x = L (L^T x) + D x, from L and d alone, or None with
+        residual=False.  The X of solve() stays as it is."""
+        b = self._thin_block(B, "lowrank_solve")
+        r = b.shape[1]
+        X = np.zeros((self.n, r), order="F")
+        res = np.zeros(r) if residual else None
+        _ck(self.D.capital_cholinv_lowrank_solve(self.p, r, b.ctypes.data_as(_dp), X.ctypes.data_as(_dp), res.ctypes.data_as(_dp) if residual else None),
+            "lowrank_solve")
+        return X, res
+
+    def lowrank_quadratic_forms(self, B):
+        """q[j] = b_j^T M^-1 b_j = sum_i b_ij^2 / d_i - ||R_c^-T L^T D^-1 b_j||^2 with the M of the last lowrank_prepare()
+        (cholesky::cholinv::lowrank_quadratic_forms, one rank): half a lowrank_solve -- one pass over L and one substitution.  B: n x r.  Returns r values."""
+        b = self._thin_block(B, "lowrank_quadratic_forms")
+        q = np.zeros(b.shape[1])
+        _ck(self.D.capital_cholinv_lowrank_quadratic_forms(self.p, b.shape[1], b.ctypes.data_as(_dp), q.ctypes.data_as(_dp)), "lowrank_quadratic_forms")
+        return q
+
+    def lowrank_logdet(self):
+        """log det (L L^T + D) = sum_i log d_i + 2 sum_i log (R_c)_ii as the last lowrank_prepare() found it"""
+        if getattr(self, "_lowrank", None) is None:
+            raise DriverError("Cholinv.lowrank_logdet: lowrank_prepare() has not run or did not succeed")
+        return self._lowrank["logdet"]
 
     def _get(self, which):
         out = np.zeros((self.n_loc, self.n_loc), order="F")

@@ -57,6 +57,9 @@ struct cholinv_problem {
   virtual void inverse_diagonal(double* d_host) = 0;
   virtual void equilibrate(double thresh, int* scaled, double* scond, double* amax, double* dscale_host) = 0;
   virtual void unequilibrate() = 0;
+  virtual void lowrank_prepare(double shift, const double* diag_host, int use_schur, double* logdet, double* cnorm1) = 0;
+  virtual void lowrank_solve(int64_t r, const double* B_host, double* X_host, double* resnorm_host) = 0;
+  virtual void lowrank_quadratic_forms(int64_t r, const double* B_host, double* q_host) = 0;
 };
 
 template <class Alg>
@@ -188,6 +191,36 @@ struct cholinv_impl : cholinv_problem {
     }
   }
   void unequilibrate() override { Alg::unequilibrate(A, pack, grid); }
+  // M = L L^T + D on the factor of the last factor_pivoted(): d = shift + diag_host (n doubles, may be NULL) + (use_schur: its remaining Schur diagonal)
+  void lowrank_prepare(double shift, const double* diag_host, int use_schur, double* logdet, double* cnorm1) override {
+    pack.lowrank_shift = shift;
+    pack.lowrank_use_schur = use_schur != 0;
+    pack.lowrank_use_diag = diag_host != nullptr;
+    if (diag_host) {
+      pack.LrDiagIn._register_(1, A.num_rows_local(), 1, 1);
+      pack.LrDiagIn.from_host(diag_host);
+    }
+    Alg::lowrank_prepare(pack, grid);
+    if (logdet) *logdet = pack.lowrank_logdet;
+    if (cnorm1) *cnorm1 = pack.lowrank_cnorm1;
+  }
+  // X_host (n x r) <- M^-1 B_host; resnorm_host (may be NULL: no residual pass) the r norms ||b_j - M x_j||_2
+  void lowrank_solve(int64_t r, const double* B_host, double* X_host, double* resnorm_host) override {
+    if (r < 1 || !B_host || !X_host) throw std::invalid_argument("cholinv lowrank_solve: r >= 1 right-hand sides, B and X expected");
+    MatrixType B(r, A.num_rows_global(), 1, 1);
+    B.from_host(B_host);
+    Alg::lowrank_solve(B, pack, grid, resnorm_host != nullptr);
+    fetch(pack.LrX, X_host);
+    if (resnorm_host) std::memcpy(resnorm_host, pack.lowrank_residual_norms.data(), sizeof(double) * (size_t)r);
+  }
+  // q_host[j] = b_j^T M^-1 b_j
+  void lowrank_quadratic_forms(int64_t r, const double* B_host, double* q_host) override {
+    if (r < 1 || !B_host || !q_host) throw std::invalid_argument("cholinv lowrank_quadratic_forms: r >= 1 columns, B and a place for the r results expected");
+    MatrixType B(r, A.num_rows_global(), 1, 1);
+    B.from_host(B_host);
+    Alg::lowrank_quadratic_forms(B, pack, grid);
+    std::memcpy(q_host, pack.lowrank_quad.data(), sizeof(double) * (size_t)r);
+  }
 };
 
 template <class SP, class IP>
@@ -440,6 +473,21 @@ int capital_cholinv_equilibrate(void* p, double thresh, int* scaled, double* sco
   return guarded([&] { ((cholinv_problem*)p)->equilibrate(thresh, scaled, scond, amax, dscale_host_or_null); });
 }
 int capital_cholinv_unequilibrate(void* p) { return guarded([&] { ((cholinv_problem*)p)->unequilibrate(); }); }
+// The regularised low-rank operator M = L L^T + D on the factor of capital_cholinv_factor_pivoted (cholesky::cholinv::lowrank_prepare / lowrank_solve /
+// lowrank_quadratic_forms; one rank): d = shift + diag_host_or_null (n doubles) + (use_schur: the remaining Schur diagonal of that factorization), every
+// d_i a finite number > 0.  prepare factors the k x k matrix C = I + L^T D^-1 L; *logdet (may be NULL) <- log det M, *cnorm1 (may be NULL) <- ||C||_1:
+// the results below carry errors of ||C||_1 2^-53.  The factors of capital_cholinv_factor and A are not touched.
+int capital_cholinv_lowrank_prepare(void* p, double shift, const double* diag_host_or_null, int use_schur, double* logdet, double* cnorm1) {
+  return guarded([&] { ((cholinv_problem*)p)->lowrank_prepare(shift, diag_host_or_null, use_schur, logdet, cnorm1); });
+}
+// X_host (n x r) <- M^-1 B_host; resnorm_host_or_null: the r norms ||b_j - M x_j||_2, from L and d alone
+int capital_cholinv_lowrank_solve(void* p, int64_t r, const double* B_host, double* X_host, double* resnorm_host_or_null) {
+  return guarded([&] { ((cholinv_problem*)p)->lowrank_solve(r, B_host, X_host, resnorm_host_or_null); });
+}
+// q_host[j] <- b_j^T M^-1 b_j, r results
+int capital_cholinv_lowrank_quadratic_forms(void* p, int64_t r, const double* B_host, double* q_host) {
+  return guarded([&] { ((cholinv_problem*)p)->lowrank_quadratic_forms(r, B_host, q_host); });
+}
 int capital_cholinv_destroy(void* p) { return guarded([&] { capital::sync(); delete (cholinv_problem*)p; }); }
 
 void* capital_cacqr_create(int64_t m, int64_t n, int c, int variant, int layout, int num_chunks, int complete_inv, int split, int bc_mult, int serialize_) {

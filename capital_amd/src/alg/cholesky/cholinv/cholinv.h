@@ -51,6 +51,12 @@
 #pragma weak capi_dpoequ2
 #pragma weak capi_dsym_scale2
 #pragma weak capi_drow_scale2
+// .. and the diagonal pieces of the low-rank operator L L^T + D: without them lowrank_prepare(), lowrank_solve() and lowrank_quadratic_forms() refuse and
+// everything else runs as before
+#pragma weak capi_dlr_diag
+#pragma weak capi_drow_pow
+#pragma weak capi_ddiag_add
+#pragma weak capi_dgemtn_ts
 
 namespace cholesky {
 
@@ -148,6 +154,21 @@ public:
     std::vector<double> dscale;
     int64_t equil_exponents = 0;
     double scond = 1.0, amax = 0.0;
+    // lowrank_prepare() / lowrank_solve() / lowrank_quadratic_forms(): the operator M = L L^T + D on factor_pivoted()'s L = Lp(:, 0:pivot_rank), with
+    // d_i = (lowrank_shift + LrDiagIn_i) + Dres_i.  Input: lowrank_shift >= 0; LrDiagIn (device, n doubles), used when lowrank_use_diag is set;
+    // lowrank_use_schur adds factor_pivoted()'s remaining Schur diagonal Dres.  Results of prepare: LrD (device, n doubles) -- d; Cap (k x k) -- R_c with
+    // C = I + L^T D^-1 L = R_c^T R_c in its upper triangle; LrGram (k x k) -- G = L^T L in its upper triangle, formed by a prepare with a uniform d
+    // (no LrDiagIn, no Schur diagonal) and kept for the next one on the same factor (lowrank_gram_valid); lowrank_logdet = log det M; lowrank_cnorm1 =
+    // ||C||_1, the error scale of every result (times u); lowrank_dmin / lowrank_dmax; lowrank_rank -- the k that was prepared; lowrank_prepared.
+    // Results of the other two: LrX (n x r) and lowrank_residual_norms; lowrank_quad and LrQuad (device: 2 r doubles, the two terms of each form).
+    // factor_pivoted() discards the prepared state and G.  None of these is read by any other operation, and args.X is not written.
+    double lowrank_shift = 0.0;
+    bool lowrank_use_schur = false, lowrank_use_diag = false;
+    matrix<ScalarType, DimensionType, rect> LrDiagIn, LrD, Cap, LrGram, LrX, LrNorm2, LrQuad;
+    bool lowrank_prepared = false, lowrank_gram_valid = false;
+    int64_t lowrank_rank = 0;
+    double lowrank_logdet = 0.0, lowrank_cnorm1 = 0.0, lowrank_dmin = 0.0, lowrank_dmax = 0.0;
+    std::vector<double> lowrank_residual_norms, lowrank_quad;
   };
 
   template <typename MatrixType, typename ArgType, typename CommType>
@@ -783,6 +804,7 @@ public:
     args.pivot_rank = 0;
     args.resid_trace = args.pivot_thresh = 0.0;
     args.pivl.clear();
+    args.lowrank_prepared = args.lowrank_gram_valid = false;       // (what lowrank_prepare() left belongs to the factor that is about to go)
     CRITTER_START(CI::factor_pivoted);
     capi_handle_t h = capital::handle();
     CAPITAL_CHECK(capi_stream_select(h, 0));
@@ -800,6 +822,182 @@ public:
     CRITTER_STOP(CI::factor_pivoted);
     if (rank == 0)
       throw std::domain_error("cholinv::factor_pivoted: numerical rank 0: no diagonal entry exceeds the threshold (A is zero or not finite)");
+  }
+
+  // ---- M = L L^T + D on the pivoted partial factor: what a user of factor_pivoted() solves with.  L = args.Lp(:, 0:k), k = args.pivot_rank, is the
+  // factor of a kernel or covariance matrix that is semidefinite or numerically low-rank -- where factor() refuses, so that solve(), log_determinant() and
+  // quadratic_forms() are closed -- and D a positive diagonal: D = sigma^2 I is Nystroem / subset-of-regressors regression, D = sigma^2 I + diag(A - L L^T)
+  // (lowrank_use_schur) is FITC.  Woodbury's identity on the k x k capacitance matrix C = I + L^T D^-1 L (SPD, lambda_min >= 1):
+  //   M^-1 B = D^-1 (B - L T),  T = C^-1 (L^T (D^-1 B));    log det M = sum log d_i + log det C;    b^T M^-1 b = sum b_i^2 / d_i - ||R_c^-T L^T D^-1 b||^2
+  // in O(n k^2) for prepare and O(n k r) per block of right-hand sides; no n x n matrix is formed and A is not read.  ONE rank.
+  // The form is NOT backward stable: its error scale is ||C||_1 u, u = 2^-53 -- not kappa(C) u: at n = k = 1 kappa(C) = 1 and the error is ||C||_1 u all the
+  // same (cancellation in B - L T) -- which is why args.lowrank_cnorm1 is handed out with every prepare.
+  // Independent of factor(), as factor_pivoted() is: R, R^-1, `factored`, `equilibrated`, args.X and A are neither read nor written. ----
+
+  // d_i = (args.lowrank_shift + LrDiagIn_i) + Dres_i (capi_dlr_diag; the vectors where args.lowrank_use_diag / lowrank_use_schur ask for them), then
+  // C = R_c^T R_c (capi_dpotrf, k <= CAPI_PCHOL_MAX_RANK) into args.Cap, args.lowrank_logdet and args.lowrank_cnorm1 (capi_dsym_abs on a vector of ones,
+  // from C's upper triangle, as condition() takes ||A||_1).  C is formed in one of two ways:
+  //   a general d     C = I + L_s^T L_s, L_s = D^-1/2 L: an n x k piece of args.ops written once by capi_drow_pow and read by capi_dsyrk
+  //   a uniform d     (no vector, no Schur diagonal): C = I + G / sigma^2 with G = L^T L by capi_dsyrk on L itself; no copy of L is made, and G stays in
+  //                   args.LrGram: the next uniform prepare on the same factor costs a k^2 scaling and the k x k factorization, no pass over L
+  // std::logic_error without a successful factor_pivoted(); std::invalid_argument for a shift that is not finite or < 0 or a vector of another length;
+  // std::domain_error naming the first d_i that is not a finite number > 0, or when capi_dpotrf meets a pivot on C (overflow or NaN only: lambda_min(C) >= 1).
+  // After any of them args.lowrank_prepared is false.  Memory, of args.ops: n k + k + 8 doubles for a general d, k + 8 for a uniform one.
+  template <typename ArgType, typename CommType>
+  static void lowrank_prepare(ArgType& args, CommType&& CommInfo) {
+    require_lowrank(args, CommInfo, "cholinv::lowrank_prepare", false);
+    args.lowrank_prepared = false;
+    const int64_t n = args.Lp.num_rows_local(), k = args.pivot_rank;
+    const double shift = args.lowrank_shift;
+    if (!std::isfinite(shift) || shift < 0.0) throw std::invalid_argument("cholinv::lowrank_prepare: lowrank_shift must be finite and >= 0");
+    if (args.lowrank_use_diag && (!args.LrDiagIn.filled() || (int64_t)args.LrDiagIn.num_elems() != n))
+      throw std::invalid_argument("cholinv::lowrank_prepare: lowrank_use_diag needs LrDiagIn with n entries");
+    const bool uniform = !args.lowrank_use_diag && !args.lowrank_use_schur;
+    CRITTER_START(CI::lowrank_prepare);
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    args.LrD._register_(1, n, 1, 1);
+    util::resize_columns(args.Cap, k, k);
+    double* const d = args.LrD.data();
+    double* const C = args.Cap.data();
+    const double* const L = args.Lp.data();
+    double rec[4], cnorm = 0.0, half = 0.0;
+    int info = 0;
+    {
+      ops_scope ops(args.ops, 0, n, (uniform ? 0 : even(n * k)) + even(k) + 8);
+      double* const Ls = uniform ? nullptr : ops.piece(n * k);
+      double* const ones = ops.piece(k);
+      double* const drec = ops.piece(4);
+      double* const small = ops.piece(4);                  // ||C||_1, sum log (R_c)_ii
+      CAPITAL_CHECK(capi_dlr_diag(h, n, shift, args.lowrank_use_diag ? args.LrDiagIn.data() : nullptr, args.lowrank_use_schur ? args.Dres.data() : nullptr, d, drec));
+      CAPITAL_CHECK(capi_memcpy_d2h(h, rec, drec, sizeof(rec)));
+      if (rec[3] == 0.0) {
+        if (uniform) {
+          if (!args.lowrank_gram_valid || !args.LrGram.filled() || args.LrGram.num_rows_local() != k) {
+            util::resize_columns(args.LrGram, k, k);
+            CAPITAL_CHECK(capi_dsyrk(h, CAPI_UPPER, CAPI_TRANS, k, n, 1.0, L, n, 0.0, args.LrGram.data(), k));
+            args.lowrank_gram_valid = true;
+          }
+          CAPITAL_CHECK(capi_dgeadd(h, 1, k, k, 1.0 / shift, args.LrGram.data(), k, 0.0, C, k));
+        } else {
+          CAPITAL_CHECK(capi_drow_pow(h, n, k, -0.5, d, 1.0, L, n, 0.0, Ls, n, nullptr));
+          CAPITAL_CHECK(capi_dsyrk(h, CAPI_UPPER, CAPI_TRANS, k, n, 1.0, Ls, n, 0.0, C, k));
+        }
+        CAPITAL_CHECK(capi_ddiag_add(h, k, 1.0, C, k));
+        {
+          const std::vector<double> one((size_t)k, 1.0);
+          CAPITAL_CHECK(capi_memcpy_h2d(h, ones, one.data(), sizeof(double) * (size_t)k));
+        }
+        CAPITAL_CHECK(capi_dsym_abs(h, k, 1, C, k, ones, k, nullptr, 0, nullptr, 0, small));
+        // (the handle's info word is factor()'s too: factor() resets it before it starts and has read it when it returns, and args.potrf_info is not touched)
+        CAPITAL_CHECK(capi_reset_info(h));
+        CAPITAL_CHECK(capi_dpotrf(h, CAPI_UPPER, k, C, k));
+        CAPITAL_CHECK(capi_get_info(h, &info));
+        if (info != 0) CAPITAL_CHECK(capi_reset_info(h));
+        CAPITAL_CHECK(capi_dtri_logdiag(h, k, C, k, 0, small + 1));
+        double out[2];
+        CAPITAL_CHECK(capi_memcpy_d2h(h, out, small, sizeof(out)));
+        cnorm = out[0]; half = out[1];
+      }
+    }
+    CRITTER_STOP(CI::lowrank_prepare);
+    if (rec[3] != 0.0)
+      throw std::domain_error("cholinv::lowrank_prepare: d_" + std::to_string((int64_t)rec[3]) + " (1-based) = shift + diag + schur is zero, negative, NaN or Inf: "
+                              "D must be a positive diagonal (a row that factor_pivoted() chose has Schur diagonal 0: give a shift > 0)");
+    if (info != 0)
+      throw std::domain_error("cholinv::lowrank_prepare: the capacitance matrix I + L^T D^-1 L is not positive definite in fp64 (pivot " + std::to_string(info) +
+                              "): it overflowed or holds a NaN");
+    args.lowrank_logdet = rec[0] + 2.0 * half;
+    args.lowrank_cnorm1 = cnorm;
+    args.lowrank_dmin = rec[1]; args.lowrank_dmax = rec[2];
+    args.lowrank_rank = k;
+    args.lowrank_prepared = true;
+  }
+
+  // args.LrX (n x r) <- M^-1 B on what lowrank_prepare() left, and, with `residual`, args.lowrank_residual_norms[j] = ||b_j - M x_j||_2 with
+  // M x = L (L^T x) + D x, from L and d alone.  B: matrix<double, int64_t, rect>(r, n, 1, 1), any r >= 1, CAPI_TS_MAX_RHS columns at a time, as solve():
+  //   W = D^-1 B (capi_drow_pow, by division), T = L^T W (capi_dgemtn_ts on L as it lies), T <- R_c^-1 R_c^-T T (capi_dtrsm_thin twice, ldt = k),
+  //   X = B - L T (capi_dresid_ts), X <- D^-1 X (in place)
+  // L is read twice per block (twice more for the residual norms) and never copied or scaled; B and args.X are not written.
+  // Memory, of args.ops: one n x CAPI_TS_MAX_RHS block and k x CAPI_TS_MAX_RHS doubles.
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void lowrank_solve(const MatrixType& B, ArgType& args, CommType&& CommInfo, bool residual = true) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::lowrank_solve takes a rect-structured B");
+    require_lowrank(args, CommInfo, "cholinv::lowrank_solve", true);
+    const int64_t n = args.Lp.num_rows_local(), k = args.lowrank_rank, r = B.num_columns_global();
+    if (r < 1 || B.num_rows_global() != n || B.num_rows_local() != n)
+      throw std::invalid_argument("cholinv::lowrank_solve: B must be n x r with r >= 1 (matrix(r, n, 1, 1))");
+    CRITTER_START(CI::lowrank_solve);
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    const int64_t W = CAPI_TS_MAX_RHS;
+    util::resize_columns(args.LrX, r, n);
+    const double *const L = args.Lp.data(), *const d = args.LrD.data(), *const Rc = args.Cap.data();
+    ops_scope ops(args.ops, 1, n, even(k * W));
+    double* const w = ops.block();
+    double* const T = ops.piece(k * W);
+    // T (k x rb) <- C^-1 (L^T V) for an n x rb block V
+    auto capacitance = [&](const double* V, int64_t rb) {
+      CAPITAL_CHECK(capi_dgemtn_ts(h, n, k, rb, 1.0, L, n, V, n, 0.0, T, k));
+      CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_TRANS, k, rb, Rc, k, 0, T, k));
+      CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_NOTRANS, k, rb, Rc, k, 0, T, k));
+    };
+    for (int64_t j = 0; j < r; j += W) {
+      const int64_t rb = std::min(W, r - j);
+      const double* Bj = B.data() + j * n;
+      double* Xj = args.LrX.data() + j * n;
+      CAPITAL_CHECK(capi_drow_pow(h, n, rb, -1.0, d, 1.0, Bj, n, 0.0, w, n, nullptr));
+      capacitance(w, rb);
+      CAPITAL_CHECK(capi_dresid_ts(h, n, k, rb, L, n, T, k, Bj, n, Xj, n, nullptr));
+      CAPITAL_CHECK(capi_drow_pow(h, n, rb, -1.0, d, 1.0, Xj, n, 0.0, Xj, n, nullptr));
+    }
+    args.lowrank_residual_norms.clear();
+    if (residual)
+      args.lowrank_residual_norms = util::residual_norms(args.LrNorm2, r, nullptr, [&](int64_t j, int64_t rb, double* norm2) {
+        const double* Xj = args.LrX.data() + j * n;
+        CAPITAL_CHECK(capi_dgemtn_ts(h, n, k, rb, 1.0, L, n, Xj, n, 0.0, T, k));                            // L^T x
+        CAPITAL_CHECK(capi_dresid_ts(h, n, k, rb, L, n, T, k, B.data() + j * n, n, w, n, nullptr));         // b - L (L^T x)
+        CAPITAL_CHECK(capi_drow_pow(h, n, rb, 1.0, d, -1.0, Xj, n, 1.0, w, n, norm2));                      // .. - D x, and its squared norms
+      });
+    CRITTER_STOP(CI::lowrank_solve);
+  }
+
+  // args.lowrank_quad[j] = b_j^T M^-1 b_j = sum_i b_ij^2 / d_i - ||R_c^-T L^T D^-1 b_j||^2: half of a lowrank_solve() -- one pass over L and one
+  // substitution.  B as there.  The two terms lie in args.LrQuad (device, 2 r doubles: the first sums, then the norms) and are subtracted on the host.
+  // sum b^2 / d is capi_drow_pow(power -1/2) with its column norms, into a work block that D^-1 B then overwrites.  B, args.X and args.LrX are not written.
+  // Memory, of args.ops: lowrank_solve()'s.
+  template <typename MatrixType, typename ArgType, typename CommType>
+  static void lowrank_quadratic_forms(const MatrixType& B, ArgType& args, CommType&& CommInfo) {
+    static_assert(std::is_same<typename MatrixType::StructureType, rect>::value, "cholinv::lowrank_quadratic_forms takes a rect-structured B");
+    require_lowrank(args, CommInfo, "cholinv::lowrank_quadratic_forms", true);
+    if (!&capi_dcolnorm2) throw std::logic_error("cholinv: this C-ABI library has no capi_dcolnorm2: no quadratic forms");
+    const int64_t n = args.Lp.num_rows_local(), k = args.lowrank_rank, r = B.num_columns_global();
+    if (r < 1 || B.num_rows_global() != n || B.num_rows_local() != n)
+      throw std::invalid_argument("cholinv::lowrank_quadratic_forms: B must be n x r with r >= 1 (matrix(r, n, 1, 1))");
+    CRITTER_START(CI::lowrank_quadratic_forms);
+    capi_handle_t h = capital::handle();
+    CAPITAL_CHECK(capi_stream_select(h, 0));
+    const int64_t W = CAPI_TS_MAX_RHS;
+    util::resize_columns(args.LrQuad, 2 * r, 1);
+    const double *const L = args.Lp.data(), *const d = args.LrD.data(), *const Rc = args.Cap.data();
+    {
+      ops_scope ops(args.ops, 1, n, even(k * W));
+      double* const w = ops.block();
+      double* const T = ops.piece(k * W);
+      for (int64_t j = 0; j < r; j += W) {
+        const int64_t rb = std::min(W, r - j);
+        const double* Bj = B.data() + j * n;
+        CAPITAL_CHECK(capi_drow_pow(h, n, rb, -0.5, d, 1.0, Bj, n, 0.0, w, n, args.LrQuad.data() + j));
+        CAPITAL_CHECK(capi_drow_pow(h, n, rb, -1.0, d, 1.0, Bj, n, 0.0, w, n, nullptr));
+        CAPITAL_CHECK(capi_dgemtn_ts(h, n, k, rb, 1.0, L, n, w, n, 0.0, T, k));
+        CAPITAL_CHECK(capi_dtrsm_thin(h, CAPI_TRANS, k, rb, Rc, k, 0, T, k));
+        CAPITAL_CHECK(capi_dcolnorm2(h, k, rb, T, k, args.LrQuad.data() + r + j));
+      }
+      const std::vector<double> terms = args.LrQuad.to_host();
+      args.lowrank_quad.resize((size_t)r);
+      for (int64_t j = 0; j < r; ++j) args.lowrank_quad[(size_t)j] = terms[(size_t)j] - terms[(size_t)(r + j)];
+    }
+    CRITTER_STOP(CI::lowrank_quadratic_forms);
   }
 
   // ---- TRSM mode -----------------------------------------------------------------------------------------------------------
@@ -1100,6 +1298,19 @@ private:
       throw std::logic_error(who + ": factor() has not run or did not succeed: there are no valid factors to solve with");
     if (args.factored_trsm != args.solve_with_trsm)
       throw std::logic_error(who + ": solve_with_trsm was changed after factor(): the resident factors are those of the other mode; factor() again");
+  }
+  // the preconditions of the operations on L L^T + D; `who` opens the message
+  template <typename ArgType, typename CommType>
+  static void require_lowrank(ArgType& args, CommType&& CommInfo, const std::string& who, bool prepared) {
+    if (CommInfo.size > 1) throw std::logic_error(who + " is built for one rank: on a grid the factors are element-cyclic (factor there, solve on one rank)");
+    if (!&capi_dlr_diag || !&capi_drow_pow || !&capi_ddiag_add)
+      throw std::logic_error("cholinv: this C-ABI library has no capi_dlr_diag / capi_drow_pow / capi_ddiag_add: no solve on the low-rank factor");
+    if (!&capi_dgemtn_ts || !&capi_dresid_ts || !&capi_dtrsm_thin || !&capi_dtri_logdiag || !&capi_dsym_abs)
+      throw std::logic_error("cholinv: this C-ABI library has no capi_dgemtn_ts / capi_dresid_ts / capi_dtrsm_thin / capi_dtri_logdiag / capi_dsym_abs: no solve on the low-rank factor");
+    if (args.pivot_rank < 1 || !args.Lp.filled() || args.pivl.empty())
+      throw std::logic_error(who + ": factor_pivoted() has not run or did not succeed: there is no low-rank factor");
+    if (prepared && (!args.lowrank_prepared || args.lowrank_rank != args.pivot_rank || !args.Cap.filled() || !args.LrD.filled()))
+      throw std::logic_error(who + ": lowrank_prepare() has not run on this factor or did not succeed");
   }
   static void require_equil_abi() {
     if (!&capi_dpoequ2 || !&capi_dsym_scale2 || !&capi_drow_scale2)

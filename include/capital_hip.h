@@ -369,6 +369,33 @@ int capi_dpchol(capi_handle_t h, int64_t n, const double* A, int64_t lda, double
 /* The threshold that capi_dpchol(h, n, A, lda, tol, ..) stops at, bit for bit (the same kernels sum the same diagonal in the same order).  Not in the
  * reference: cholinv.hpp stops at R and R^-1.  Reads A's diagonal alone; CAPI_EINVAL as there, with nothing touched. */
 int capi_dpchol_thresh(capi_handle_t h, int64_t n, const double* A, int64_t lda, double tol, double* thresh_host);
+/* ---- the diagonal pieces of M = L L^T + D on capi_dpchol's factor, D a positive diagonal (cholesky::cholinv::lowrank_prepare / lowrank_solve /
+ * lowrank_quadratic_forms: Woodbury's identity with the k x k matrix C = I + L^T D^-1 L; the products, the Cholesky factorization of C and the
+ * substitutions run on capi_dsyrk, capi_dpotrf, capi_dgemtn_ts, capi_dtrsm_thin and capi_dresid_ts).  Not in the reference: cholinv.hpp stops at R and R^-1.
+ * The three calls share the conventions of the thin calls: DEVICE pointers, column-major, pointers aligned to 8 bytes; a null handle returns -1 before any
+ * device call; bad arguments return CAPI_EINVAL before any launch, nothing is touched; a size of 0 is a no-op; no atomics, sums in one fixed order
+ * (two calls on the same bits give the same bytes).  No workspace. ----
+ * capi_dlr_diag: d[i] (n doubles) <- (shift + diag[i]) + schur[i], each sum rounded, in that order; diag == NULL and schur == NULL count as zeros (they are
+ * not added).  Not in the reference: cholinv.hpp stops at R and R^-1.  rec (4 doubles): rec[0] = sum_i log d_i, rec[1] = min d, rec[2] = max d, rec[3] = 0 --
+ * or rec[3] = j + 1 for the FIRST j whose d_j is not a finite number > 0 (zero, negative, NaN, Inf): then rec[0 .. 2] are 0, d is unspecified and a caller
+ * refuses.  rec[3] is a word of its own, not the handle's potrf info word (capi_get_info).  One workgroup; a thread adds the logarithms of the entries
+ * tid, tid + 1024, .., the sums meet in a butterfly inside the wave and the 16 waves in order (capi_dpoequ2's and capi_dtri_logdiag's style). */
+int capi_dlr_diag(capi_handle_t h, int64_t n, double shift, const double* diag, const double* schur, double* d, double* rec);
+/* capi_drow_pow: Y <- alpha diag(d)^power X + beta Y on an m x r block, any r >= 1, power = +1, -1 or -0.5 (anything else: CAPI_EINVAL).
+ * Not in the reference: cholinv.hpp stops at R and R^-1.  ldx, ldy >= m; Y == X is allowed with ldy == ldx; with beta == 0 Y is not read (it may hold NaN).
+ * Order of the operations, every one rounded on its own (no fused multiply-add), t the scaled element:
+ *   power +1: t = x d;  power -1: t = x / d (a division per element);  power -0.5: t = x w with w = 1 / sqrt(d), taken once per row;
+ *   Y = alpha t + beta y (beta == 0: Y = alpha t)
+ * so that +1 and -1 give numpy's alpha * (x * d) + beta * y and alpha * (x / d) + beta * y bit for bit, and -0.5 is within 2 ulp of x / sqrt(d).
+ * norm2: NULL, or r doubles that receive the squared column norms of the result Y, by a pass of its own in capi_dcolnorm2's fixed order (one workgroup
+ * per column); with NULL nothing but Y is written.  16-byte accesses where X and Y are 16-byte aligned and ldx, ldy are even, 8-byte ones otherwise;
+ * the padding rows m .. ld - 1 are neither read into a result nor written.  d must be positive where power < 0 (no check: a zero gives Inf or NaN).
+ * A pure stream: 512 rows x 32 (or 8) columns per workgroup, a row's factor computed once. */
+int capi_drow_pow(capi_handle_t h, int64_t m, int64_t r, double power, const double* d, double alpha, const double* X, int64_t ldx, double beta, double* Y,
+                  int64_t ldy, double* norm2);
+/* capi_ddiag_add: C(i, i) += alpha for i < n (ldc >= n): the I of C = I + L^T D^-1 L.  Not in the reference: cholinv.hpp stops at R and R^-1.  Nothing off
+ * the diagonal is read or written. */
+int capi_ddiag_add(capi_handle_t h, int64_t n, double alpha, double* C, int64_t ldc);
 /* LAPACKE_dgeqrf / LAPACKE_dorgqr behind lapack::engine::_geqrf / _orgqr (lapack/interface.hpp:60-88; the reference has
  * the slots but no caller -- CholeskyQR2 is its QR).  Householder QR, LAPACK storage: R in the upper triangle, the
  * reflectors v_j (unit first entry implied) below it, tau[min(m,n)] on the DEVICE.  capi_dorgqr overwrites A (m x n,
