@@ -86,6 +86,10 @@ def bind(D):
     D.capital_cacqr_svd.argtypes = [_vp, _int, _dp, _dp, _dp, C.POINTER(_int)]
     D.capital_cacqr_factor_pivoted.argtypes = [_vp, _dbl, _dbl, C.POINTER(_int)]
     D.capital_cacqr_get_piv.argtypes = [_vp, C.POINTER(_i64)]
+    _tail = [_i64, _dbl, _dp, C.POINTER(_int)]             # pad, fill, pad rows out, (x, y, z, d, c) out
+    D.capital_summa_gemm.argtypes = [_int] * 5 + [_i64] * 3 + [_dbl, _dbl, _dp, _dp, _dp] + _tail
+    D.capital_summa_trmm.argtypes = [_int] * 7 + [_i64] * 2 + [_dbl, _dp, _dp, _dp] + _tail
+    D.capital_summa_syrk.argtypes = [_int] * 5 + [_i64] * 2 + [_dbl, _dbl, _dp, _dp] + _tail
     return D
 
 
@@ -153,6 +157,72 @@ def world_query():
     r, s = _int(), _int()
     _ck(load().capital_drv_world_query(C.byref(r), C.byref(s)), "world_query")
     return r.value, s.value
+
+
+SUMMA_FILL = -1.2345678901234567e+100      # what the pad rows of a view-mode block hold before a summa_* call
+
+
+def _summa_block(a):
+    a = np.asfortranarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.size == 0:
+        raise DriverError(f"summa: a non-empty two-dimensional local block expected, got shape {a.shape}")
+    return a
+
+
+def _summa_tail(pad, cols, fill):
+    rows = np.zeros((pad, cols), order="F") if pad > 0 else None
+    return rows, (_int * 5)(), [int(pad), float(fill), rows.ctypes.data_as(_dp) if pad > 0 else None]
+
+
+def summa_gemm(A, B, C0, transA=False, transB=False, alpha=1.0, beta=0.0, c=1, layout=0, num_chunks=0, pad=0, fill=SUMMA_FILL):
+    """One matmult::summa gemm on the d x d x c grid over the current world: alpha op(A) op(B) + beta C0 on this rank's LOCAL blocks (INTEGRATION.md,
+    "SUMMA on a grid": which block of a global operand a rank holds).  Every rank calls.  pad=0: the public summa::invoke overload on matrix<>
+    objects; pad>0: the view-level engine on device blocks of leading dimension rows + pad whose pad rows hold `fill`.  Returns (C, pad_rows,
+    (x, y, z, d, c)): pad_rows are C's pad rows after the call (pad x N), None with pad=0."""
+    a, b, c0 = _summa_block(A), _summa_block(B), _summa_block(C0)
+    M, N = c0.shape
+    K = a.shape[0] if transA else a.shape[1]
+    if a.shape != ((K, M) if transA else (M, K)) or b.shape != ((N, K) if transB else (K, N)):
+        raise DriverError(f"summa_gemm: blocks {a.shape}, {b.shape}, {c0.shape} do not fit transA={transA}, transB={transB}")
+    out = c0.copy(order="F")
+    rows, where, tail = _summa_tail(pad, N, fill)
+    _ck(load().capital_summa_gemm(c, layout, num_chunks, int(bool(transA)), int(bool(transB)), M, N, K, float(alpha), float(beta),
+                                  a.ctypes.data_as(_dp), b.ctypes.data_as(_dp), out.ctypes.data_as(_dp), *tail, where), "summa_gemm")
+    return out, rows, tuple(where)
+
+
+def summa_trmm(T, B, C0=None, side="L", uplo="U", trans=False, unit=False, alpha=1.0, c=1, layout=0, num_chunks=0, pad=0, fill=SUMMA_FILL):
+    """One matmult::summa trmm: alpha op(T) B (side "L") or alpha B op(T) ("R") with this rank's block T of a triangular matrix, of which only
+    the `uplo` triangle is read (and not the diagonal where unit=True and the block is a diagonal one).  C0: what the output block holds before a
+    view-mode call (default zeros; the public overload multiplies in place).  Returns (C, pad_rows, (x, y, z, d, c)); pad_rows are B's."""
+    t, b = _summa_block(T), _summa_block(B)
+    M, N = b.shape
+    nt = M if side == "L" else N
+    if side not in ("L", "R") or uplo not in ("U", "L") or t.shape != (nt, nt):
+        raise DriverError(f"summa_trmm: side L or R, uplo U or L and a T of order {nt} expected, got {side!r}, {uplo!r}, {t.shape}")
+    out = np.zeros((M, N), order="F") if C0 is None else _summa_block(C0).copy(order="F")
+    if out.shape != (M, N):
+        raise DriverError(f"summa_trmm: C0 must be {M} x {N}, got {out.shape}")
+    rows, where, tail = _summa_tail(pad, N, fill)
+    _ck(load().capital_summa_trmm(c, layout, num_chunks, capi.LEFT if side == "L" else capi.RIGHT, capi.UPPER if uplo == "U" else capi.LOWER,
+                                  int(bool(trans)), capi.UNIT if unit else capi.NONUNIT, M, N, float(alpha), t.ctypes.data_as(_dp),
+                                  b.ctypes.data_as(_dp), out.ctypes.data_as(_dp), *tail, where), "summa_trmm")
+    return out, rows, tuple(where)
+
+
+def summa_syrk(A, C0, uplo="U", trans=True, alpha=1.0, beta=0.0, c=1, layout=0, num_chunks=0, pad=0, fill=SUMMA_FILL):
+    """One matmult::summa syrk: the `uplo` triangle of this rank's block of alpha A^T A + beta C0 (trans=True, A K x N) or alpha A A^T + beta C0
+    (A N x K); the rest of the block comes back as it went in.  Returns (C, pad_rows, (x, y, z, d, c)); pad_rows are C's."""
+    a, c0 = _summa_block(A), _summa_block(C0)
+    N = c0.shape[0]
+    K = a.shape[0] if trans else a.shape[1]
+    if uplo not in ("U", "L") or c0.shape != (N, N) or a.shape != ((K, N) if trans else (N, K)):
+        raise DriverError(f"summa_syrk: blocks {a.shape}, {c0.shape} do not fit trans={trans}, or uplo {uplo!r} is neither U nor L")
+    out = c0.copy(order="F")
+    rows, where, tail = _summa_tail(pad, N, fill)
+    _ck(load().capital_summa_syrk(c, layout, num_chunks, capi.UPPER if uplo == "U" else capi.LOWER, int(bool(trans)), N, K, float(alpha), float(beta),
+                                  a.ctypes.data_as(_dp), out.ctypes.data_as(_dp), *tail, where), "summa_syrk")
+    return out, rows, tuple(where)
 
 
 class Cholinv:

@@ -351,6 +351,79 @@ struct cacqr_impl : cacqr_problem {
   }
 };
 
+// ---- one SUMMA multiply on the current world (capital_summa_gemm / _trmm / _syrk below) ----------------------------------------------
+using matmult::summa;
+using matmult::view;
+
+// the d x d x c grid of the multiplies: its four sub-communicators are kept between calls while c, layout and CAPITAL_MULTIPATH (read when
+// a grid is built) stay what they were; num_chunks is set per call
+struct summa_grid_cache {
+  std::unique_ptr<topo::square> grid;
+  int c = 0, layout = 0;
+  std::string multipath;
+};
+CAPITAL_RANK_LOCAL summa_grid_cache g_summa_grid;
+
+topo::square& summa_grid(int c, int layout, int num_chunks) {
+  if (c < 1 || layout < 0 || num_chunks < 0) throw std::invalid_argument("summa: c >= 1, layout >= 0 and num_chunks >= 0 expected");
+  if (!capital::world()) throw std::runtime_error("no world communicator: call capital_drv_init first");
+  const char* mp = getenv("CAPITAL_MULTIPATH");
+  summa_grid_cache& g = g_summa_grid;
+  if (!g.grid || g.c != c || g.layout != layout || g.multipath != (mp ? mp : "")) {
+    capital::sync();
+    g.grid.reset();
+    g.grid.reset(new topo::square(capital::world(), (size_t)c, (size_t)layout, 0));
+    g.c = c; g.layout = layout; g.multipath = mp ? mp : "";
+  }
+  g.grid->num_chunks = (size_t)num_chunks;
+  return *g.grid;
+}
+void summa_grid_where(const topo::square& t, int* xyzdc) {
+  if (!xyzdc) return;
+  xyzdc[0] = (int)t.x; xyzdc[1] = (int)t.y; xyzdc[2] = (int)t.z; xyzdc[3] = (int)t.d; xyzdc[4] = (int)t.c;
+}
+
+// a rows x cols block on the device with leading dimension rows + pad; the pad rows below every column hold `fill`
+struct padded_block {
+  double* p = nullptr;
+  int64_t rows, cols, ld;
+  padded_block(const double* host, int64_t rows_, int64_t cols_, int64_t pad, double fill) : rows(rows_), cols(cols_), ld(rows_ + pad) {
+    std::vector<double> img((size_t)(ld * cols), fill);
+    for (int64_t j = 0; j < cols; ++j) std::memcpy(&img[(size_t)(j * ld)], host + j * rows, sizeof(double) * (size_t)rows);
+    p = capital::dev_alloc(ld * cols);
+    CAPITAL_CHECK(capi_memcpy_h2d(capital::handle(), p, img.data(), sizeof(double) * img.size()));
+  }
+  padded_block(const padded_block&) = delete;
+  padded_block& operator=(const padded_block&) = delete;
+  ~padded_block() { capital::dev_free(p); }
+  view v() const { return view{p, ld, rows, cols}; }
+  // the block into block_host (rows x cols) and its pad rows into pad_host ((ld - rows) x cols), both column-major; either may be NULL
+  void fetch(double* block_host, double* pad_host) const {
+    std::vector<double> img((size_t)(ld * cols));
+    CAPITAL_CHECK(capi_memcpy_d2h(capital::handle(), img.data(), p, sizeof(double) * img.size()));
+    const int64_t pad = ld - rows;
+    for (int64_t j = 0; j < cols; ++j) {
+      if (block_host) std::memcpy(block_host + j * rows, &img[(size_t)(j * ld)], sizeof(double) * (size_t)rows);
+      if (pad_host && pad > 0) std::memcpy(pad_host + j * pad, &img[(size_t)(j * ld + rows)], sizeof(double) * (size_t)pad);
+    }
+  }
+};
+
+// a matrix<> of the given LOCAL extents filled from the host (what the public summa::invoke overloads take)
+MatrixType local_matrix(const double* host, int64_t rows, int64_t cols) {
+  MatrixType m(nullptr, cols, rows, 1, 1);
+  m.from_host(host);
+  return m;
+}
+
+// the arena of a view-level call: the public overloads' rules over the padded extents, the relay space of a grid of pairs and, for syrk, the
+// exchanged copy with its staging on top
+matmult::arena& summa_view_arena(int64_t a, int64_t b, int64_t c) {
+  matmult::arena& ws = summa::scratch_arena();
+  ws.reserve(6 * (a + b + c) + 1024);
+  return ws;
+}
+
 }  // namespace
 
 extern "C" {
@@ -371,7 +444,15 @@ int capital_drv_init(int device, int rank, int size, const void* uid, void* stre
     }
   });
 }
-int capital_drv_finalize(void) { return guarded([] { capital::finalize(); }); }
+int capital_drv_finalize(void) {
+  return guarded([] {
+    if (g_summa_grid.grid) {                                     // (its sub-communicators go before the world they were split from)
+      if (capital::ctx().handle) capital::sync();
+      g_summa_grid.grid.reset();
+    }
+    capital::finalize();
+  });
+}
 int capital_drv_sync(void) { return guarded([] { capital::sync(); }); }
 void* capital_drv_handle(void) { return capital::ctx().handle; }
 // rank and size of the world communicator as RCCL itself reports them (a launcher prints them next to its own)
@@ -527,5 +608,94 @@ int capital_cacqr_get(void* p, int which, double* host) { return guarded([&] { (
 int capital_cacqr_get_rows(void* p, int which, int64_t row0, int64_t nrows, double* host) { return guarded([&] { ((cacqr_problem*)p)->get_rows(which, row0, nrows, host); }); }
 int capital_cacqr_dims(void* p, int64_t* mloc, int64_t* n) { return guarded([&] { ((cacqr_problem*)p)->dims(mloc, n); }); }
 int capital_cacqr_destroy(void* p) { return guarded([&] { capital::sync(); delete (cacqr_problem*)p; }); }
+
+// One matmult::summa multiply on the d x d x c grid over the current world (every rank calls, with the same arguments but its own blocks):
+// what cholinv and cacqr issue many of, alone -- any form, any alpha and beta.  All extents are LOCAL, all host blocks column-major without
+// padding; the flags are the C-ABI's (CAPI_TRANS, CAPI_LEFT, CAPI_UPPER, CAPI_UNIT ...).  INTEGRATION.md, "SUMMA on a grid", says which block of
+// the global operands a rank passes.  pad == 0: through the public summa::invoke overloads on matrix<> objects (their arena sizing, the in-place
+// TRMM, the SYRK that exchanges with the transpose partner itself).  pad > 0: through the view-level gemm / trmm / syrk on device blocks of
+// leading dimension rows + pad whose pad rows hold `fill`; pad_host (pad x columns, may be NULL) then receives the pad rows of the block named
+// below as they are after the call.  xyzdc (may be NULL) receives this rank's x, y, z and the grid's d, c.
+// C_host (M x N): in C0, out alpha op(A) op(B) + beta C0; A_host is M x K (transA: K x M), B_host K x N (transB: N x K); pad_host: C's pad rows
+int capital_summa_gemm(int c, int layout, int num_chunks, int transA, int transB, int64_t M, int64_t N, int64_t K, double alpha, double beta,
+                       const double* A_host, const double* B_host, double* C_host, int64_t pad, double fill, double* pad_host, int* xyzdc) {
+  return guarded([&] {
+    if (M < 1 || N < 1 || K < 1 || pad < 0 || !A_host || !B_host || !C_host) throw std::invalid_argument("summa gemm: positive extents, pad >= 0 and the three blocks expected");
+    topo::square& t = summa_grid(c, layout, num_chunks);
+    summa_grid_where(t, xyzdc);
+    const int64_t ar = transA ? K : M, ac = transA ? M : K, br = transB ? N : K, bc = transB ? K : N;
+    if (pad == 0) {
+      MatrixType A = local_matrix(A_host, ar, ac), B = local_matrix(B_host, br, bc), C = local_matrix(C_host, M, N);
+      blas::ArgPack_gemm<T> pack(blas::Order::AblasColumnMajor, transA ? blas::Transpose::AblasTrans : blas::Transpose::AblasNoTrans,
+                                 transB ? blas::Transpose::AblasTrans : blas::Transpose::AblasNoTrans, alpha, beta);
+      summa::invoke(A, B, C, t, pack);
+      capital::sync();
+      fetch(C, C_host);
+      return;
+    }
+    padded_block A(A_host, ar, ac, pad, fill), B(B_host, br, bc, pad, fill), C(C_host, M, N, pad, fill);
+    matmult::arena& ws = summa_view_arena(A.ld * ac, B.ld * bc, C.ld * N);
+    summa::gemm(t, transA ? CAPI_TRANS : CAPI_NOTRANS, transB ? CAPI_TRANS : CAPI_NOTRANS, alpha, A.v(), B.v(), beta, C.v(), ws);
+    capital::sync();
+    C.fetch(C_host, pad_host);
+  });
+}
+// C_host (M x N): in what the output block holds before the call (view mode: the output is a block of its own, contiguous as summa.h asks; the
+// public overload multiplies in place), out alpha op(T) B (side Left, T of order M) or alpha B op(T) (Right, order N); pad_host: B's pad rows
+int capital_summa_trmm(int c, int layout, int num_chunks, int side, int uplo, int trans, int diag, int64_t M, int64_t N, double alpha,
+                       const double* T_host, const double* B_host, double* C_host, int64_t pad, double fill, double* pad_host, int* xyzdc) {
+  return guarded([&] {
+    if (M < 1 || N < 1 || pad < 0 || !T_host || !B_host || !C_host) throw std::invalid_argument("summa trmm: positive extents, pad >= 0 and the three blocks expected");
+    topo::square& t = summa_grid(c, layout, num_chunks);
+    summa_grid_where(t, xyzdc);
+    const int64_t nt = side == CAPI_LEFT ? M : N;
+    if (pad == 0) {
+      MatrixType A = local_matrix(T_host, nt, nt), B = local_matrix(B_host, M, N);
+      blas::ArgPack_trmm<T> pack(blas::Order::AblasColumnMajor, side == CAPI_LEFT ? blas::Side::AblasLeft : blas::Side::AblasRight,
+                                 uplo == CAPI_UPPER ? blas::UpLo::AblasUpper : blas::UpLo::AblasLower,
+                                 trans ? blas::Transpose::AblasTrans : blas::Transpose::AblasNoTrans,
+                                 diag == CAPI_UNIT ? blas::Diag::AblasUnit : blas::Diag::AblasNonUnit, alpha);
+      summa::invoke(A, B, t, pack);
+      capital::sync();
+      fetch(B, C_host);
+      return;
+    }
+    padded_block Tb(T_host, nt, nt, pad, fill), B(B_host, M, N, pad, fill), Cout(C_host, M, N, 0, fill);
+    matmult::arena& ws = summa_view_arena(Tb.ld * nt, B.ld * N, M * N);
+    summa::trmm(t, side, uplo, trans ? CAPI_TRANS : CAPI_NOTRANS, diag, alpha, Tb.v(), B.v(), Cout.v(), ws);
+    capital::sync();
+    Cout.fetch(C_host, nullptr);
+    B.fetch(nullptr, pad_host);
+  });
+}
+// C_host (N x N): in C0, out -- in its `uplo` triangle alone -- alpha A^T A + beta C0 (trans; A_host K x N) or alpha A A^T + beta C0 (A_host N x K);
+// the second operand is this rank's A exchanged with the transpose partner, as cholinv.h prepares it (view mode) or as the public overload does;
+// pad_host: C's pad rows
+int capital_summa_syrk(int c, int layout, int num_chunks, int uplo, int trans, int64_t N, int64_t K, double alpha, double beta,
+                       const double* A_host, double* C_host, int64_t pad, double fill, double* pad_host, int* xyzdc) {
+  return guarded([&] {
+    if (N < 1 || K < 1 || pad < 0 || !A_host || !C_host) throw std::invalid_argument("summa syrk: positive extents, pad >= 0 and the two blocks expected");
+    topo::square& t = summa_grid(c, layout, num_chunks);
+    summa_grid_where(t, xyzdc);
+    const int64_t ar = trans ? K : N, ac = trans ? N : K;
+    if (pad == 0) {
+      MatrixType A = local_matrix(A_host, ar, ac), C = local_matrix(C_host, N, N);
+      blas::ArgPack_syrk<T> pack(blas::Order::AblasColumnMajor, uplo == CAPI_UPPER ? blas::UpLo::AblasUpper : blas::UpLo::AblasLower,
+                                 trans ? blas::Transpose::AblasTrans : blas::Transpose::AblasNoTrans, alpha, beta);
+      summa::invoke(A, C, t, pack);
+      capital::sync();
+      fetch(C, C_host);
+      return;
+    }
+    padded_block A(A_host, ar, ac, pad, fill), C(C_host, N, N, pad, fill);
+    matmult::arena& ws = summa_view_arena(A.ld * ac, 0, C.ld * N);
+    view Ax{ws.take(ar * ac), ar, ar, ac};
+    CAPITAL_CHECK(capi_dlacpy(capital::handle(), 0, ar, ac, A.p, A.ld, Ax.p, Ax.ld));
+    util::transpose_raw(Ax.p, Ax.count(), ws.take(Ax.count()), t, summa::relay_space(t, Ax.count(), ws));
+    summa::syrk(t, uplo, trans ? CAPI_TRANS : CAPI_NOTRANS, alpha, A.v(), Ax, beta, C.v(), ws);
+    capital::sync();
+    C.fetch(C_host, pad_host);
+  });
+}
 
 }  // extern "C"

@@ -378,7 +378,7 @@ public:
         view tt, bb;
         if (side == CAPI_LEFT) { tt = panel_tri(t, AX_ROW, s, T, uplo, ws); bb = panel(t, AX_COLUMN, s, B, ws); }
         else { bb = panel(t, AX_ROW, s, B, ws); tt = panel_tri(t, AX_COLUMN, s, T, uplo, ws); }
-        CAPITAL_CHECK(capi_dtrmm_acc(h, side, uplo, trans, diag, M, N, alpha, tt.p, tt.ld, bb.p, bb.ld, s ? 1.0 : 0.0, Cout.p, Cout.ld));
+        CAPITAL_CHECK(capi_dtrmm_acc(h, side, uplo, trans, diag_of_step(t, side, diag, s), M, N, alpha, tt.p, tt.ld, bb.p, bb.ld, s ? 1.0 : 0.0, Cout.p, Cout.ld));
       }
     } else {
       // the T panels of every K-class step first (whole, packed), then the B panels column chunk by column chunk
@@ -395,13 +395,14 @@ public:
         double* Cj = Cout.p + c0 * Cout.ld;
         for (size_t s = 0; c1 > c0 && s < steps; ++s) {
           const double b0 = s ? 1.0 : 0.0;
+          const int dg = diag_of_step(t, side, diag, s);
           if (side == CAPI_LEFT) {
-            CAPITAL_CHECK(capi_dtrmm_acc(h, side, uplo, trans, diag, M, c1 - c0, alpha, tt[s].p, tt[s].ld, bb[s].p + c0 * bb[s].ld, bb[s].ld, b0, Cj, Cout.ld));
+            CAPITAL_CHECK(capi_dtrmm_acc(h, side, uplo, trans, dg, M, c1 - c0, alpha, tt[s].p, tt[s].ld, bb[s].p + c0 * bb[s].ld, bb[s].ld, b0, Cj, Cout.ld));
           } else {
             // Cout[:, chunk] += alpha ( B[:, 0:c0] T[0:c0, chunk] + B[:, chunk] T[chunk, chunk] ): a rectangle above the chunk's triangle
             if (c0 > 0)
               CAPITAL_CHECK(capi_dgemm(h, CAPI_NOTRANS, CAPI_NOTRANS, M, c1 - c0, c0, alpha, bb[s].p, bb[s].ld, tt[s].p + c0 * tt[s].ld, tt[s].ld, b0, Cj, Cout.ld));
-            CAPITAL_CHECK(capi_dtrmm_acc(h, side, uplo, trans, diag, M, c1 - c0, alpha, tt[s].p + c0 + c0 * tt[s].ld, tt[s].ld, bb[s].p + c0 * bb[s].ld, bb[s].ld,
+            CAPITAL_CHECK(capi_dtrmm_acc(h, side, uplo, trans, dg, M, c1 - c0, alpha, tt[s].p + c0 + c0 * tt[s].ld, tt[s].ld, bb[s].p + c0 * bb[s].ld, bb[s].ld,
                                          (c0 > 0 || s) ? 1.0 : 0.0, Cj, Cout.ld));
           }
         }
@@ -587,6 +588,14 @@ public:
   // is this rank the root of the broadcast along `axis` at K-class step s?  (layer z owns K-classes z, z + c, ...)
   template <typename CommType>
   static bool is_root(CommType&& t, int axis, size_t s) { return (axis == AX_ROW ? t.x : t.y) == t.z + s * t.c; }
+  // The diagonal flag of the local TRMM at K-class step s on d > 1.  The block of op(T) that meets this rank's output block at K-class q holds
+  // a piece of the GLOBAL diagonal, on its own diagonal, only where q is the output block's row class (Left: op(T) is rows x K) or column class
+  // (Right: K x columns); every other block's diagonal holds entries of T's triangle proper or stored zeros of the other one, which a unit flag
+  // must not replace by ones.
+  template <typename CommType>
+  static int diag_of_step(CommType&& t, int side, int diag, size_t s) {
+    return (side == CAPI_LEFT ? t.y : t.x) == t.z + s * t.c ? diag : (int)CAPI_NONUNIT;
+  }
 
   // ---- pair collectives: over every link of the node (capi_pairs_transfer, csrc/pair_paths.h) when the grid's rows / columns /
   //      depth fibres are pairs, else as RCCL calls on the sub-communicators ---------------------------------------------------------

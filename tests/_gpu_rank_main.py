@@ -31,6 +31,23 @@ def main():
             os.environ.pop(k, None)
         os.environ.update(case.get("env", {}))
         print(f"rank {rank}: case {tag} starts", flush=True)
+        if case["kind"] == "summa":
+            # every SUMMA multiply of tests/_summa_cases.py (tests/test_gpu_summa.py), each under its own switches; this rank cuts its blocks from
+            # the seeded global operands and keeps its results for the parent
+            sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+            import _summa_cases as SC
+            res = {}
+            for one in SC.cases(case.get("only")):
+                for k in SC.ENV_KEYS:
+                    os.environ.pop(k, None)
+                os.environ.update(one["env"])
+                print(f"rank {rank}: {one['tag']}", flush=True)
+                res.update(SC.run_case(driver, one, rank, world))
+            for k in SC.ENV_KEYS:
+                os.environ.pop(k, None)
+            np.savez(os.path.join(cfg["dir"], f"{tag}_rank{rank}.npz"), **res)
+            dist.barrier()
+            continue
         if case["kind"] == "cholinv":
             p = driver.Cholinv(case["n"], c=case["c"], complete_inv=case["ci"], split=1, bc_mult=case["bc"], layout=case.get("layout", 0),
                                num_chunks=case.get("chunks", 0), serialize=case["serialize"], bc_policy=case["policy"], trsm_mode=case.get("trsm", False))

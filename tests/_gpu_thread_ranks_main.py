@@ -15,6 +15,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _summa_cases as SC  # noqa: E402  (the SUMMA case table: numpy only)
 
 
 T0 = time.time()
@@ -61,6 +63,25 @@ def main():
                     os.environ.update(case.get("env", {}))
                     print(f"process {proc}: case {tag} starts at +{time.time() - T0:.1f} s", flush=True)
                 bar.wait()
+                if case["kind"] == "summa":
+                    # every SUMMA multiply of tests/_summa_cases.py (tests/test_gpu_summa.py); the process's environment changes between two
+                    # multiplies, while all of its threads stand at the barrier
+                    res = {}
+                    for one in SC.cases(case.get("only")):
+                        bar.wait()
+                        if t == 0:
+                            for k in SC.ENV_KEYS:
+                                os.environ.pop(k, None)
+                            os.environ.update(one["env"])
+                            print(f"process {proc}: {one['tag']}", flush=True)
+                        bar.wait()
+                        res.update(SC.run_case(driver, one, rank, world))
+                    bar.wait()
+                    if t == 0:
+                        for k in SC.ENV_KEYS:
+                            os.environ.pop(k, None)
+                    np.savez(os.path.join(cfg["dir"], f"{tag}_rank{rank}.npz"), **res)
+                    continue
                 if case["kind"] == "cholinv":
                     p = driver.Cholinv(case["n"], c=case["c"], complete_inv=case["ci"], split=1, bc_mult=case["bc"], layout=case.get("layout", 0),
                                        num_chunks=case.get("chunks", 0), serialize=case["serialize"], bc_policy=case["policy"], trsm_mode=case.get("trsm", False))

@@ -122,6 +122,26 @@ def main():
     lib.capi_shim_set_collective(keep)
     assert lib.capital_drv_init(0, rank, world, None, None) == 0, lib.capital_drv_last_error()
     out = {"rank": rank}
+    if cfg["kind"] == "summa":
+        # every SUMMA multiply of tests/_summa_cases.py, one after the other, each under its own switches; this rank cuts its blocks from the
+        # seeded global operands and keeps its results for the parent
+        sys.path.insert(0, os.path.dirname(HERE))
+        import _summa_cases as SC
+        res = {}
+        for case in SC.cases(cfg.get("only")):
+            for k in SC.ENV_KEYS:
+                os.environ.pop(k, None)
+            os.environ.update(case["env"])
+            try:
+                res.update(SC.run_case(driver, case, rank, world))
+            except Exception:
+                print(f"rank {rank}: case {case['tag']} failed", flush=True)
+                raise
+        np.savez(os.path.join(cfg["dir"], f"rank{rank}.npz"), **res)
+        lib.capital_drv_finalize()
+        dist.barrier()
+        dist.destroy_process_group()
+        return
     if cfg["kind"] == "cholinv":
         p = driver.Cholinv(cfg["n"], c=cfg["c"], complete_inv=cfg["ci"], split=cfg.get("split", 1), bc_mult=cfg["bc"],
                            layout=cfg.get("layout", 0), num_chunks=cfg.get("chunks", 0), serialize=cfg["serialize"], bc_policy=cfg["policy"],

@@ -230,11 +230,12 @@ def test_async_transport_catches_a_missing_consumer_wait(oracle):
 THREAD_DRIVER = os.path.join(HERE, "thread_ranks", "libcapital_driver_threads.so")
 
 
-def _launch_thread_ranks(nproc, threads, cfg, mode, timeout=int(os.environ.get("CAPITAL_TEST_RANK_TIMEOUT_S", "900"))):
+def _launch_thread_ranks(nproc, threads, cfg, mode, timeout=int(os.environ.get("CAPITAL_TEST_RANK_TIMEOUT_S", "900")), extra_env=None):
     procs = []
     for p in range(nproc):
         env = dict(os.environ, PROC_INDEX=str(p), NPROC=str(nproc), THREADS_PER_PROC=str(threads), HSA_ENABLE_IPC_MODE_LEGACY="0",
                    CAPITAL_MIN_CHUNK_COLS="64", CAPI_RCCL_LIB=LOOPBACK, CAPI_LOOPBACK_MODE=mode, CAPITAL_DRIVER_LIB=THREAD_DRIVER)
+        env.update(extra_env or {})
         # Every HIP stream of every rank needs a hardware queue of its OWN: the HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES
         # (default 4) queues, and two ranks whose streams share a queue deadlock in the asynchronous mode -- rank A's device-side wait for rank B's
         # message blocks the very queue B's copy kernel sits in (measured: 2 processes x 4 threads stall in the first case; host-staged mode passes)
@@ -299,3 +300,17 @@ def test_eight_ranks_as_threads_2x2x2_grid_and_cacqr_3d(oracle, mode):
     with tempfile.TemporaryDirectory() as d:
         _launch_thread_ranks(4, 2, {"dir": d, "cases": cases}, mode)
         _check_cases(oracle, d, cases, world, c)
+
+
+def test_summa_eight_ranks_as_threads_2x2x2():
+    """The 2 x 2 x 2 case of tests/test_gpu_summa.py (it stands in THIS file because the session runs this file first, see there): matmult::summa's
+    gemm, trmm and syrk in every form on the cubic grid -- K-class broadcasts, depth sums, packed triangles and the multi-path transfer sets at
+    P = 8 -- over the asynchronous transport; every multiply of tests/_summa_cases.py in one launch, each against the longdouble product of the
+    global operands."""
+    import _summa_cases as SC
+    from capital_amd import driver
+    subprocess.check_call(["make", "-C", os.path.dirname(LOOPBACK), "-s"])
+    subprocess.check_call(["make", "-C", os.path.dirname(THREAD_DRIVER), "-s"])
+    with tempfile.TemporaryDirectory() as d:
+        _launch_thread_ranks(4, 2, {"dir": d, "cases": [{"tag": "summa", "kind": "summa"}]}, "async", extra_env={"CAPITAL_MIN_CHUNK_COLS": SC.MIN_CHUNK_COLS})
+        SC.check_launch(8, d, "summa_rank{}.npz", driver.SUMMA_FILL)
