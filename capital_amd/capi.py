@@ -93,6 +93,8 @@ _SIGS = {
     "capi_sync": [],
     "capi_dgeqrf": [_i64, _i64, _vp, _i64, _vp],
     "capi_dorgqr": [_i64, _i64, _i64, _vp, _i64, _vp],
+    "capi_dormqr": [_int, _int, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64],
+    "capi_dgels": [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, C.POINTER(_int)],
     "capi_reserve_workspace": [C.c_size_t],
     "capi_trim_workspaces": [],
     "capi_set_launch_rounds": [_int, C.POINTER(_int)],

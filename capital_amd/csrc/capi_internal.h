@@ -111,5 +111,9 @@ static inline int capi_thin_rb(int64_t r) { return r > 16 ? 2 : 1; }
 // CUs the selected stream may use: its CU mask's, or all
 static inline int capi_stream_cus(capi_handle_t h) { return h->cu_of[h->cur] > 0 ? h->cu_of[h->cur] : h->num_cu; }
 
+// capi_dormqr's path beyond CAPI_TS_MAX_RHS columns: the block-reflector loop of qr_f64.hip (arguments checked by the caller, side = CAPI_LEFT)
+int capi_qr_apply_wide(capi_handle_t h, int trans, int64_t m, int64_t r, int64_t k, const double* A, int64_t lda, const double* tau, double* C,
+                       int64_t ldc);
+
 // hipFree, or (CAPI_DEFER_FREE) remember the block until capi_destroy
 hipError_t capi_release(capi_handle_t h, void* p);

@@ -574,3 +574,23 @@ int capi_dorgqr(capi_handle_t h, int64_t m, int64_t n, int64_t k, double* A, int
 }
 
 }  // extern "C"
+
+// capi_dormqr beyond CAPI_TS_MAX_RHS columns (qr_apply_f64.hip): C (m x r) <- Q^T C or Q C by the loop capi_dorgqr runs per panel, the block
+// reflectors in ascending order with T^T for Q^T, in descending order with T for Q.  A is not written.
+int capi_qr_apply_wide(capi_handle_t h, int trans, int64_t m, int64_t r, int64_t k, const double* A, int64_t lda, const double* tau, double* C,
+                       int64_t ldc) {
+  qr_ws w;
+  RC(qr_workspace(h, m, r, false, w));
+  const int64_t np = cdiv(k, QNB);
+  for (int64_t step = 0; step < np; ++step) {
+    const int64_t j0 = (trans == CAPI_TRANS ? step : np - 1 - step) * QNB;
+    const int nb = (int)(k - j0 < QNB ? k - j0 : QNB);
+    const int64_t rows = m - j0;
+    double* Cs = C + j0;
+    RC(block_reflector(h, A + j0 + j0 * lda, lda, rows, nb, tau + j0, w));
+    RC(capi_dgemm(h, CAPI_TRANS, CAPI_NOTRANS, nb, r, rows, 1.0, w.Vw, rows, Cs, ldc, 0.0, w.W, nb));
+    RC(capi_dgemm(h, trans == CAPI_TRANS ? CAPI_TRANS : CAPI_NOTRANS, CAPI_NOTRANS, nb, r, nb, 1.0, w.T, nb, w.W, nb, 0.0, w.W2, nb));
+    RC(capi_dgemm(h, CAPI_NOTRANS, CAPI_NOTRANS, rows, r, nb, -1.0, w.Vw, rows, w.W2, nb, 1.0, Cs, ldc));
+  }
+  return CAPI_OK;
+}

@@ -12,7 +12,9 @@ namespace lapack {
 enum class Order : unsigned char { AlapackRowMajor = 0x0, AlapackColumnMajor = 0x1 };
 enum class UpLo : unsigned char { AlapackLower = 0x0, AlapackUpper = 0x1 };
 enum class Diag : unsigned char { AlapackNonUnit = 0x0, AlapackUnit = 0x1 };
-enum class Method : unsigned char { AlapackPotrf = 0x0, AlapackTrtri = 0x1, AlapackGeqrf = 0x10, AlapackOrgqr = 0x11 };
+enum class Side : unsigned char { AlapackLeft = 0x0, AlapackRight = 0x1 };
+enum class Trans : unsigned char { AlapackNoTrans = 0x0, AlapackTrans = 0x1 };
+enum class Method : unsigned char { AlapackPotrf = 0x0, AlapackTrtri = 0x1, AlapackGeqrf = 0x10, AlapackOrgqr = 0x11, AlapackOrmqr = 0x12, AlapackGels = 0x13 };
 
 class ArgPack {
 public:
@@ -41,6 +43,19 @@ public:
   explicit ArgPack_orgqr(Order o) : order(o) { method = Method::AlapackOrgqr; }
   Order order;
 };
+// not in the reference (lapack/interface.h declares _geqrf and _orgqr only): the third member of the Householder path and the solve on it
+class ArgPack_ormqr : public ArgPack {
+public:
+  ArgPack_ormqr(Order o, Side s, Trans t) : order(o), side(s), trans(t) { method = Method::AlapackOrmqr; }
+  Order order;
+  Side side;
+  Trans trans;
+};
+class ArgPack_gels : public ArgPack {
+public:
+  explicit ArgPack_gels(Order o) : order(o) { method = Method::AlapackGels; }
+  Order order;
+};
 
 class engine {
 public:
@@ -55,6 +70,13 @@ public:
   static void _geqrf(T* A, T* tau, int m, int n, int lda, const ArgPack_geqrf& p);
   template <typename T>
   static void _orgqr(T* A, T* tau, int m, int n, int k, int lda, const ArgPack_orgqr& p);
+  // C (m x r, ldc) <- Q^T C or Q C, Q = H_1 .. H_k of the _geqrf image A (m x k, lda) and tau; side Left only.  DEVICE pointers.
+  template <typename T>
+  static void _ormqr(const T* A, const T* tau, T* C, int m, int r, int k, int lda, int ldc, const ArgPack_ormqr& p);
+  // min ||A X - B||, m >= n: A and tau leave as _geqrf's image, B (m x r, ldb) as [X; tail of Q^T B]; colnorm2 (DEVICE, r values, or null) receives
+  // the squared residual norms.  Returns LAPACK's info: 0, or the 1-based index of the first zero or non-finite diagonal entry of R (no solve then).
+  template <typename T>
+  static int _gels(T* A, T* tau, T* B, T* colnorm2, int m, int n, int r, int lda, int ldb, const ArgPack_gels& p);
   // synchronises; 0 or the 1-based index of the first non-positive pivot since the last reset
   static int info() { int v = 0; CAPITAL_CHECK(capi_get_info(capital::handle(), &v)); return v; }
   static void reset_info() { CAPITAL_CHECK(capi_reset_info(capital::handle())); }
@@ -80,6 +102,18 @@ template <>
 inline void engine::_orgqr(double* A, double* tau, int m, int n, int k, int lda, const ArgPack_orgqr& p) {
   if (p.order != Order::AlapackColumnMajor) throw std::invalid_argument("lapack::engine: only AlapackColumnMajor is served");
   CAPITAL_CHECK(capi_dorgqr(capital::handle(), m, n, k, A, lda, tau));
+}
+template <>
+inline void engine::_ormqr(const double* A, const double* tau, double* C, int m, int r, int k, int lda, int ldc, const ArgPack_ormqr& p) {
+  if (p.order != Order::AlapackColumnMajor) throw std::invalid_argument("lapack::engine: only AlapackColumnMajor is served");
+  CAPITAL_CHECK(capi_dormqr(capital::handle(), (int)p.side, (int)p.trans, m, r, k, A, lda, tau, C, ldc));
+}
+template <>
+inline int engine::_gels(double* A, double* tau, double* B, double* colnorm2, int m, int n, int r, int lda, int ldb, const ArgPack_gels& p) {
+  if (p.order != Order::AlapackColumnMajor) throw std::invalid_argument("lapack::engine: only AlapackColumnMajor is served");
+  int info = 0;
+  CAPITAL_CHECK(capi_dgels(capital::handle(), m, n, r, A, lda, tau, B, ldb, colnorm2, &info));
+  return info;
 }
 
 }  // namespace lapack

@@ -404,6 +404,33 @@ int capi_ddiag_add(capi_handle_t h, int64_t n, double alpha, double* C, int64_t 
  * dlarfg's on either side of that gate, tau = 0 for a column that is already reduced included.  k == 0: tau may be NULL. */
 int capi_dgeqrf(capi_handle_t h, int64_t m, int64_t n, double* A, int64_t lda, double* tau);
 int capi_dorgqr(capi_handle_t h, int64_t m, int64_t n, int64_t k, double* A, int64_t lda, const double* tau);
+/* capi_dormqr: LAPACK's dormqr for side == CAPI_LEFT: C (m x r, ldc >= m) <- Q^T C (CAPI_TRANS) or Q C (CAPI_NOTRANS) with Q = H_1 ... H_k taken from
+ * the first k columns of a capi_dgeqrf image A (m x k, lda >= m, m >= k >= 0) and tau (DEVICE, k doubles), without forming Q.  Not in the reference:
+ * lapack/interface.h declares _geqrf and _orgqr only.  side == CAPI_RIGHT (C Q, C Q^T) is not served: CAPI_EINVAL.  A is not written.  Nothing on or
+ * above A's diagonal influences the result -- that part holds R, and NaN there is harmless: the unit diagonal and the zeros above it are put in by a
+ * select, never by a multiplication by zero.  tau[j] == 0 is the identity reflector and takes no special path.  Any other bad argument (a null operand
+ * of a non-empty problem, lda < m, ldc < m, k > m): CAPI_EINVAL before any launch, nothing is touched.  m == 0, r == 0 or k == 0: nothing happens
+ * (tau may be NULL when k == 0).  Pointers aligned to 8 bytes, any leading dimensions (16 bytes and even leading dimensions take the faster loads);
+ * the padding rows m .. ld - 1 of C are neither read into a result nor written.  The handle's info word is not touched.
+ * r <= CAPI_TS_MAX_RHS: panels of 32 reflectors, ascending for Q^T and descending for Q, three launches each (csrc/ormqr_plan.h): P^T [P | C] over the
+ * panel's live rows in one pass on v_mfma_f64_16x16x4_f64 (row slices per workgroup, slabs added in slab order), one workgroup for T (dlarft's
+ * recurrence), Z = T^T W or T W and the panel's top 32 rows, and capi_dresid_ts for C -= P Z below them.  The panel is read from HBM twice, the live
+ * rows of C twice and written once; no m-long temporary.  Sums have a fixed order: no atomics, the same bits on every run.  Workspace, of the handle's
+ * own: 8 KiB + at most (CUs) x 14 KiB.  r > CAPI_TS_MAX_RHS: the block-reflector loop of capi_dorgqr on the tile kernel (capi_dorgqr's workspace). */
+int capi_dormqr(capi_handle_t h, int side, int trans, int64_t m, int64_t r, int64_t k, const double* A, int64_t lda, const double* tau, double* C,
+                int64_t ldc);
+/* capi_dgels: LAPACK's dgels(trans = 'N') for m >= n >= 1 and any r >= 1: min ||A X - B|| by Householder QR, backward stable up to kappa(A) ~ 1 / u.
+ * Not in the reference: lapack/interface.h declares _geqrf and _orgqr only.  m < n (minimum-norm solutions) is not served: CAPI_EINVAL, nothing is
+ * touched.  On exit A and tau (DEVICE, n doubles) hold capi_dgeqrf's image, so further right-hand sides can follow through capi_dormqr +
+ * capi_dtrsm_thin; rows 0 .. n - 1 of B (m x r, ldb >= m) hold X, rows n .. m - 1 the tail of Q^T B; colnorm2 (DEVICE, r doubles, or NULL) receives the
+ * squared residual norms, the column sums of squares of that tail (zeros when m == n).  *info_host is 0, or the 1-based index of the first diagonal
+ * entry of R that is exactly zero or not finite: B is then left as Q^T B, no solve is done and colnorm2 is not written (rank-deficient problems:
+ * qr::cacqr::factor_pivoted).  The steps: capi_dgeqrf (CholeskyQR2 + reconstruction or the Householder panels, by its own choice),
+ * capi_dormqr(CAPI_LEFT, CAPI_TRANS), a one-workgroup scan of R's diagonal, capi_dtrsm_thin(CAPI_NOTRANS) on R in place in A in column blocks of at most
+ * CAPI_TS_MAX_RHS (substitution, no inverse), capi_dcolnorm2 on the tail.  Reading *info_host is the call's own stream synchronisation (capi_dgeqrf
+ * has its own). */
+int capi_dgels(capi_handle_t h, int64_t m, int64_t n, int64_t r, double* A, int64_t lda, double* tau, double* B, int64_t ldb, double* colnorm2,
+               int* info_host);
 int capi_reset_info(capi_handle_t h);
 
 /* ---- data movement: replaces serialize<> (src/matrix/serialize.hpp:12-150), the pack/unpack and
