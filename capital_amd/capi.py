@@ -95,6 +95,8 @@ _SIGS = {
     "capi_dorgqr": [_i64, _i64, _i64, _vp, _i64, _vp],
     "capi_dormqr": [_int, _int, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64],
     "capi_dgels": [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, C.POINTER(_int)],
+    "capi_dgeqp3": [_i64, _i64, _vp, _i64, _vp, _vp, _dbl, C.POINTER(_int)],
+    "capi_dgelsy": [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _dbl, _int, _vp, C.POINTER(_int)],
     "capi_reserve_workspace": [C.c_size_t],
     "capi_trim_workspaces": [],
     "capi_set_launch_rounds": [_int, C.POINTER(_int)],

@@ -1,5 +1,5 @@
-// qr_apply_f64.hip -- capi_dormqr and capi_dgels for gfx950: Q or Q^T of a capi_dgeqrf image applied to a block without forming Q, and the
-// Householder least-squares solve built on it.  Not in the reference: lapack/interface.h declares _geqrf and _orgqr only.
+// qr_apply_f64.hip -- capi_dormqr, capi_dgels and capi_dgelsy for gfx950: Q or Q^T of a capi_dgeqrf image applied to a block without forming Q, the
+// Householder least-squares solve built on it, and the rank-revealing one (capi_dgeqp3 of qrcp_f64.hip on the n x n triangle).  Not in the reference: lapack/interface.h declares _geqrf and _orgqr only.
 //
 // THIN PATH (r <= CAPI_TS_MAX_RHS): panels of 32 reflectors (csrc/ormqr_plan.h), three launches per panel at j0, P = the unit lower trapezoid of
 // A[j0:m, j0:j0+nb] and Cp = C[j0:m, :]:
@@ -235,6 +235,31 @@ __global__ __launch_bounds__(256) void gels_diag_scan_kernel(const double* __res
   if (threadIdx.x == 0) *info = first[0] == 0x7fffffff ? 0 : first[0];
 }
 
+// Z (n x k, ldz) <- [R11 R12]^T from the upper trapezoid of capi_dgeqp3's image F: Z(i, l) = F(l, i) for i >= l, an exact zero above (what lies below
+// F's diagonal, the reflectors, is not read).  32 x 32 tiles through LDS: reads run down F's columns, writes down Z's
+__global__ __launch_bounds__(256) void gelsy_transpose_kernel(int n, int k, const double* __restrict__ F, int64_t ldf, double* __restrict__ Z, int64_t ldz) {
+  __shared__ double tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int i0 = blockIdx.x * 32, l0 = blockIdx.y * 32;                     // tile: rows l0 .. of F (columns of Z), columns i0 .. of F (rows of Z)
+  for (int q = ty; q < 32; q += 8) {
+    const int l = l0 + tx, i = i0 + q;
+    tile[q][tx] = (l < k && i < n && i >= l) ? F[l + (int64_t)i * ldf] : 0.0;
+  }
+  __syncthreads();
+  for (int q = ty; q < 32; q += 8) {
+    const int i = i0 + tx, l = l0 + q;
+    if (i < n && l < k) Z[i + (int64_t)l * ldz] = tile[tx][q];
+  }
+}
+
+// rows r0 .. r1 - 1 of B (ldb, ncols columns) <- 0
+__global__ __launch_bounds__(256) void gelsy_zero_rows_kernel(int64_t r0, int64_t r1, int64_t ncols, double* __restrict__ B, int64_t ldb) {
+  const int64_t i = r0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= r1) return;
+  for (int64_t j = blockIdx.y; j < ncols; j += gridDim.y) B[i + j * ldb] = 0.0;
+}
+
+bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int ormqr_thin(capi_handle_t h, int trans, int64_t m, int64_t r, int64_t k, const double* A, int64_t lda, const double* tau, double* C, int64_t ldc) {
@@ -304,6 +329,48 @@ int capi_dgels(capi_handle_t h, int64_t m, int64_t n, int64_t r, double* A, int6
     if (colnorm2) RC(capi_dcolnorm2(h, m - n, rb, B + n + j * ldb, ldb, colnorm2 + j));
   }
   return CAPI_OK;
+}
+
+int capi_dgelsy(capi_handle_t h, int64_t m, int64_t n, int64_t r, double* A, int64_t lda, double* tau, double* F, int64_t ldf, double* tauf, int* jpvt,
+                double* Z, int64_t ldz, double* tauz, double* B, int64_t ldb, double rcond, int min_norm, double* colnorm2, int* rank_host) {
+  CAPI_REQUIRE(h, h, "null handle");
+  CAPI_REQUIRE(h, n >= 1 && m >= n && n <= CAPI_GEQP3_MAX && r >= 1 && m < (1LL << 31) && r < (1LL << 31), "dims (m >= n >= 1, n <= CAPI_GEQP3_MAX, r >= 1)");
+  CAPI_REQUIRE(h, A && tau && F && tauf && jpvt && B && rank_host && lda >= m && ldf >= n && ldb >= m, "operands");
+  CAPI_REQUIRE(h, min_norm == 0 || (Z && tauz && ldz >= n), "Z / tauz / ldz >= n (they may be NULL only with min_norm == 0)");
+  CAPI_REQUIRE(h, rcond == rcond, "rcond is not a number");
+  CAPI_REQUIRE(h, aligned8(A) && aligned8(tau) && aligned8(F) && aligned8(tauf) && aligned8(B) && aligned8(Z) && aligned8(tauz) && aligned8(colnorm2) &&
+                      ((uintptr_t)jpvt & 3) == 0, "pointers aligned to 8 bytes (jpvt to 4)");
+  RC(capi_dgeqrf(h, m, n, A, lda, tau));
+  RC(capi_dormqr(h, CAPI_LEFT, CAPI_TRANS, m, r, n, A, lda, tau, B, ldb));
+  RC(capi_dlacpy(h, 1, n, n, A, lda, F, ldf));
+  RC(capi_dtrizero(h, CAPI_UPPER, n, F, ldf));
+  int k = 0;
+  RC(capi_dgeqp3(h, n, n, F, ldf, jpvt, tauf, rcond < 0.0 ? (double)m * 0x1p-52 : rcond, &k));   // the call's synchronisation
+  *rank_host = k;
+  RC(capi_dormqr(h, CAPI_LEFT, CAPI_TRANS, n, r, k, F, ldf, tauf, B, ldb));
+  const bool mn = min_norm != 0 && k < n && k > 0;
+  if (mn) {
+    hipLaunchKernelGGL(gelsy_transpose_kernel, dim3((unsigned)cdiv(n, 32), (unsigned)cdiv(k, 32)), dim3(256), 0, h->stream, (int)n, k, (const double*)F, ldf, Z, ldz);
+    CAPI_HIP_CHECK(h, hipGetLastError());
+    RC(capi_dgeqrf(h, n, k, Z, ldz, tauz));
+  }
+  for (int64_t j = 0; j < r; j += CAPI_TS_MAX_RHS) {
+    const int64_t rb = r - j < CAPI_TS_MAX_RHS ? r - j : CAPI_TS_MAX_RHS;
+    double* Bj = B + j * ldb;
+    if (colnorm2) RC(capi_dcolnorm2(h, m - k, rb, Bj + k, ldb, colnorm2 + j));
+    if (k > 0) RC(capi_dtrsm_thin(h, mn ? CAPI_TRANS : CAPI_NOTRANS, k, rb, mn ? Z : F, mn ? ldz : ldf, 0, Bj, ldb));
+  }
+  if (mn) {
+    const unsigned gy = (unsigned)(r < 65535 ? r : 65535);
+    hipLaunchKernelGGL(gelsy_zero_rows_kernel, dim3((unsigned)cdiv(n - k, 256), gy), dim3(256), 0, h->stream, (int64_t)k, n, r, B, ldb);
+    CAPI_HIP_CHECK(h, hipGetLastError());
+    RC(capi_dormqr(h, CAPI_LEFT, CAPI_NOTRANS, n, r, k, Z, ldz, tauz, B, ldb));
+  }
+  // X = P Y: the scatter must not run in place
+  void* pv = nullptr;
+  RC(capi_ws_get(h, sizeof(double) * (size_t)n * (size_t)r, &pv));
+  RC(capi_drow_scatter(h, 0, mn ? n : k, r, n, B, ldb, jpvt, (double*)pv, n));
+  return capi_dlacpy(h, 0, n, r, (const double*)pv, n, B, ldb);
 }
 
 }  // extern "C"

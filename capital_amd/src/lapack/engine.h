@@ -14,7 +14,8 @@ enum class UpLo : unsigned char { AlapackLower = 0x0, AlapackUpper = 0x1 };
 enum class Diag : unsigned char { AlapackNonUnit = 0x0, AlapackUnit = 0x1 };
 enum class Side : unsigned char { AlapackLeft = 0x0, AlapackRight = 0x1 };
 enum class Trans : unsigned char { AlapackNoTrans = 0x0, AlapackTrans = 0x1 };
-enum class Method : unsigned char { AlapackPotrf = 0x0, AlapackTrtri = 0x1, AlapackGeqrf = 0x10, AlapackOrgqr = 0x11, AlapackOrmqr = 0x12, AlapackGels = 0x13 };
+enum class Method : unsigned char { AlapackPotrf = 0x0, AlapackTrtri = 0x1, AlapackGeqrf = 0x10, AlapackOrgqr = 0x11, AlapackOrmqr = 0x12, AlapackGels = 0x13,
+                                     AlapackGeqp3 = 0x14, AlapackGelsy = 0x15 };
 
 class ArgPack {
 public:
@@ -56,6 +57,18 @@ public:
   explicit ArgPack_gels(Order o) : order(o) { method = Method::AlapackGels; }
   Order order;
 };
+// the rank-revealing pair: column-pivoted QR of a block of order <= CAPI_GEQP3_MAX, and least squares for A of any rank (basic or minimum-norm solution)
+class ArgPack_geqp3 : public ArgPack {
+public:
+  explicit ArgPack_geqp3(Order o) : order(o) { method = Method::AlapackGeqp3; }
+  Order order;
+};
+class ArgPack_gelsy : public ArgPack {
+public:
+  ArgPack_gelsy(Order o, bool mn) : order(o), min_norm(mn) { method = Method::AlapackGelsy; }
+  Order order;
+  bool min_norm;
+};
 
 class engine {
 public:
@@ -77,6 +90,16 @@ public:
   // the squared residual norms.  Returns LAPACK's info: 0, or the 1-based index of the first zero or non-finite diagonal entry of R (no solve then).
   template <typename T>
   static int _gels(T* A, T* tau, T* B, T* colnorm2, int m, int n, int r, int lda, int ldb, const ArgPack_gels& p);
+  // W (mr x n, ldw) <- the LAPACK image of W P = Q R, jpvt (DEVICE, n ints, 0-based), tau (DEVICE, min(mr, n)); stops at the first pivot column whose
+  // norm is <= rtol times the first one's (rtol < 0: max(mr, n) 2^-52).  Returns the rank.
+  template <typename T>
+  static int _geqp3(T* W, int* jpvt, T* tau, int mr, int n, int ldw, T rtol, const ArgPack_geqp3& p);
+  // min ||A X - B|| for A (m x n, m >= n) of any rank: A, tau as _geqrf leaves them; F (n x n, ldf), tauf, jpvt as _geqp3 leaves them on R1; with
+  // p.min_norm Z (n x n room, ldz) and tauz hold the factorization of [R11 R12]^T (else they may be null); B (m x r, ldb) leaves as [X; tail of Q1^T B];
+  // colnorm2 (DEVICE, r values, or null) receives the squared residual norms.  Returns the rank.
+  template <typename T>
+  static int _gelsy(T* A, T* tau, T* F, T* tauf, int* jpvt, T* Z, T* tauz, T* B, T* colnorm2, int m, int n, int r, int lda, int ldf, int ldz, int ldb,
+                    T rcond, const ArgPack_gelsy& p);
   // synchronises; 0 or the 1-based index of the first non-positive pivot since the last reset
   static int info() { int v = 0; CAPITAL_CHECK(capi_get_info(capital::handle(), &v)); return v; }
   static void reset_info() { CAPITAL_CHECK(capi_reset_info(capital::handle())); }
@@ -114,6 +137,21 @@ inline int engine::_gels(double* A, double* tau, double* B, double* colnorm2, in
   int info = 0;
   CAPITAL_CHECK(capi_dgels(capital::handle(), m, n, r, A, lda, tau, B, ldb, colnorm2, &info));
   return info;
+}
+template <>
+inline int engine::_geqp3(double* W, int* jpvt, double* tau, int mr, int n, int ldw, double rtol, const ArgPack_geqp3& p) {
+  if (p.order != Order::AlapackColumnMajor) throw std::invalid_argument("lapack::engine: only AlapackColumnMajor is served");
+  int rank = 0;
+  CAPITAL_CHECK(capi_dgeqp3(capital::handle(), mr, n, W, ldw, jpvt, tau, rtol, &rank));
+  return rank;
+}
+template <>
+inline int engine::_gelsy(double* A, double* tau, double* F, double* tauf, int* jpvt, double* Z, double* tauz, double* B, double* colnorm2, int m, int n,
+                          int r, int lda, int ldf, int ldz, int ldb, double rcond, const ArgPack_gelsy& p) {
+  if (p.order != Order::AlapackColumnMajor) throw std::invalid_argument("lapack::engine: only AlapackColumnMajor is served");
+  int rank = 0;
+  CAPITAL_CHECK(capi_dgelsy(capital::handle(), m, n, r, A, lda, tau, F, ldf, tauf, jpvt, Z, ldz, tauz, B, ldb, rcond, p.min_norm ? 1 : 0, colnorm2, &rank));
+  return rank;
 }
 
 }  // namespace lapack

@@ -425,12 +425,71 @@ int capi_dormqr(capi_handle_t h, int side, int trans, int64_t m, int64_t r, int6
  * capi_dtrsm_thin; rows 0 .. n - 1 of B (m x r, ldb >= m) hold X, rows n .. m - 1 the tail of Q^T B; colnorm2 (DEVICE, r doubles, or NULL) receives the
  * squared residual norms, the column sums of squares of that tail (zeros when m == n).  *info_host is 0, or the 1-based index of the first diagonal
  * entry of R that is exactly zero or not finite: B is then left as Q^T B, no solve is done and colnorm2 is not written (rank-deficient problems:
- * qr::cacqr::factor_pivoted).  The steps: capi_dgeqrf (CholeskyQR2 + reconstruction or the Householder panels, by its own choice),
+ * capi_dgelsy below, or qr::cacqr::factor_pivoted on the Gram matrix).  The steps: capi_dgeqrf (CholeskyQR2 + reconstruction or the Householder panels, by its own choice),
  * capi_dormqr(CAPI_LEFT, CAPI_TRANS), a one-workgroup scan of R's diagonal, capi_dtrsm_thin(CAPI_NOTRANS) on R in place in A in column blocks of at most
  * CAPI_TS_MAX_RHS (substitution, no inverse), capi_dcolnorm2 on the tail.  Reading *info_host is the call's own stream synchronisation (capi_dgeqrf
  * has its own). */
 int capi_dgels(capi_handle_t h, int64_t m, int64_t n, int64_t r, double* A, int64_t lda, double* tau, double* B, int64_t ldb, double* colnorm2,
                int* info_host);
+/* capi_dgeqp3: QR with column pivoting of a small block, W P = Q R, LAPACK's dgeqp3 in dlaqp2's unblocked form: the rank-revealing step of capi_dgelsy,
+ * run on the n x n triangle that capi_dgeqrf leaves (pivoted QR of R1 itself resolves rank down to u ||A||, where the Gram route of capi_dpstrf stops at
+ * sqrt(u)).  Not in the reference: lapack/interface.h declares _geqrf and _orgqr only.  W is mr x n, column-major, DEVICE, ldw >= mr,
+ * 1 <= mr, n <= CAPI_GEQP3_MAX.  On exit W holds the image of W P in LAPACK storage: with k the rank, rows < k of the upper trapezoid hold R, below the
+ * diagonal of columns < k lie the reflectors (unit first entry implied); tau (DEVICE, min(mr, n) doubles) has tau[j] = 0 for j >= k; jpvt (DEVICE, n
+ * ints, 0-based) is always a full permutation: column j of W P is column jpvt[j] of the input (capi_dpstrf's convention).  *rank_host = k; reading it
+ * ends the call (the stream is also synchronised once per round of 64 steps, to read a 4-byte stop flag: the only host traffic).  A null handle
+ * returns -1; any other bad argument (a null operand, ldw < mr, a size out of range, a NaN rtol, W or tau not aligned to 8 bytes) returns CAPI_EINVAL
+ * before any launch, with nothing touched; mr == 0 or n == 0: rank 0, nothing is launched.  The handle's info word is not touched.
+ * The step rule.  Running norms vn1 = vn2 = the column norms at the start.  At step j = 0, 1, ..:
+ *   pivot     p is the FIRST index, under the total order on (value, original index) -- the larger value, ties to the smaller index -- of the largest
+ *             running norm vn1 among the columns not yet chosen; a NaN is entered as -inf;
+ *   norm      nu = ||W(j:mr, p)||_2 is recomputed from the column itself in a fixed summation order: sqrt(alpha^2 + s2), alpha = W(j, p), s2 the sum
+ *             of squares below it; nu_0 is the value at step 0;
+ *   stop      the factorization stops at rank j unless nu > rtol * nu_0 && nu > 0 -- written so that a NaN compares false and stops.  rtol = 0 stops
+ *             only at an exactly zero remainder; rtol < 0 means max(mr, n) 2^-52.  The rank rule is this threshold on |r_jj| = nu, NOT dgelsy's
+ *             incremental condition estimator;
+ *   reflector dlarfg's, without its rescaling of tiny columns: beta = -sign(alpha) nu, tau = (beta - alpha) / beta, v = x / (alpha - beta); when
+ *             everything below alpha is zero (s2 == 0) it is tau = 0, beta = alpha -- the form capi_dgeqrf gives such a column;
+ *   update    a_c -= tau v (v^T a_c) on rows >= j of every column not chosen; then dlaqp2's two-vector downdate of its running norm:
+ *             temp = max(0, 1 - (|a_jc| / vn1)^2), temp2 = temp (vn1 / vn2)^2; temp2 <= tol3z = sqrt(2^-53): vn1 = vn2 = ||a_c(j+1:mr)||_2
+ *             recomputed from the column; otherwise vn1 *= sqrt(temp).  A column with vn1 == 0 keeps it.
+ * After a stop rows >= k of columns >= k keep the unreduced remainder (the columns never chosen go behind the chosen ones in ascending order of their
+ * original index); its columns have norm <= rtol nu_0 up to the downdate's accuracy.  Every loop's trip count is fixed by mr and n, so non-finite
+ * input ends the call like any other: CAPI_OK, 0 <= k <= min(mr, n), jpvt a permutation, the values unspecified.
+ * Method (csrc/qrcp_f64.hip): swap-free, one launch per step over ceil(n / 8) workgroups of 256 threads; a wave owns two columns through the whole
+ * call; every workgroup reduces the per-workgroup (value, index) candidates the launch before left and forms nu, beta, tau and v itself from the
+ * read-only pivot column (v staged in LDS, 16 KiB at most), so all hold the same bits; the pivot's owner writes column j of the image to a second
+ * mr x n block; a last launch pair places the columns never chosen, writes jpvt and copies the image back.  A stop sets a device flag; later launches
+ * read it at entry and return.  Ordered by kernel boundaries on the handle's stream alone: no cooperative launch, no device-side waiting, no atomics;
+ * sums have a fixed order: two calls on the same bits give identical bytes.  Workspace, of the handle's own: 8 mr n + 20 n + 32 ceil(n / 8) + 16 bytes. */
+enum { CAPI_GEQP3_MAX = 2048 };
+int capi_dgeqp3(capi_handle_t h, int64_t mr, int64_t n, double* W, int64_t ldw, int* jpvt, double* tau, double rtol, int* rank_host);
+/* capi_dgelsy: LAPACK's dgelsy for m >= n >= 1, n <= CAPI_GEQP3_MAX and any r >= 1: min ||A X - B|| for A of ANY rank -- the basic solution (nonzeros
+ * in the k pivot columns only) or the minimum-norm one.  Not in the reference: lapack/interface.h declares _geqrf and _orgqr only.  All pointers are
+ * DEVICE pointers, aligned to 8 bytes (jpvt to 4).  Everything of size m runs on capi_dgeqrf and capi_dormqr; only the n x n triangle R1 is pivoted:
+ * A = Q1 R1, R1 P = Q2 R, so A P = (Q1 Q2) R, and the rank k is read off |r_jj| > rcond |r_00| (capi_dgeqp3's rule, rcond < 0: max(m, n) 2^-52; no
+ * incremental condition estimator).  The steps:
+ *   1. capi_dgeqrf(A, tau): on exit the image and tau are bit for bit those of a separate capi_dgeqrf call;
+ *   2. capi_dormqr(CAPI_LEFT, CAPI_TRANS) on B (m x r, ldb >= m);
+ *   3. F (n x n, ldf >= n) <- triu(R1), zeros below (capi_dlacpy, capi_dtrizero);
+ *   4. capi_dgeqp3(n, n, F, ldf, jpvt, tauf, rcond, &k): F, tauf (n doubles) and jpvt (n ints) as that call leaves them;
+ *   5. capi_dormqr(CAPI_LEFT, CAPI_TRANS, n, r, k, F, ldf, tauf, B, ldb) on the top n rows of B;
+ *   6. colnorm2 (r doubles, or NULL) <- capi_dcolnorm2 over rows k .. m - 1 of B, the squared residual norms;
+ *   7. basic (min_norm == 0, or k == n): Y = R11^-1 C by capi_dtrsm_thin(CAPI_NOTRANS, k, ..) on F in column blocks of at most CAPI_TS_MAX_RHS;
+ *      minimum norm (min_norm != 0 and k < n): Z (n x k, ldz >= n) <- [R11 R12]^T, capi_dgeqrf(n, k, Z, ldz, tauz), T^T y = c by
+ *      capi_dtrsm_thin(CAPI_TRANS, k, ..) on Z, rows k .. n - 1 of the top block <- 0, capi_dormqr(CAPI_LEFT, CAPI_NOTRANS, n, r, k, Z, ldz, tauz, B, ldb);
+ *   8. X = P Y by capi_drow_scatter through the handle's workspace (n r doubles), copied into rows 0 .. n - 1 of B.
+ * On exit rows n .. m - 1 of B keep the tail of Q1^T B; *rank_host = k.  k == 0 (A zero): X = 0, colnorm2 = the squared column norms of Q1^T B,
+ * CAPI_OK.  Z and tauz (k doubles, so n suffice) may be NULL iff min_norm == 0.  m < n, n > CAPI_GEQP3_MAX, a null or misaligned argument, a leading
+ * dimension too small, a NaN rcond: CAPI_EINVAL before any launch, nothing is touched (as capi_dgels refuses).  The handle's info word is not touched.
+ * FURTHER RIGHT-HAND SIDES on the factors left in A, tau, F, tauf, jpvt, Z and tauz, by public calls alone (capital_amd.hqr.Hqr.lstsq_pivoted):
+ *   capi_dormqr(CAPI_LEFT, CAPI_TRANS, m, r, n, A, lda, tau, B, ldb); capi_dormqr(CAPI_LEFT, CAPI_TRANS, n, r, k, F, ldf, tauf, B, ldb);
+ *   capi_dcolnorm2(m - k, rb, B + k, ldb, ..) per block of rb <= CAPI_TS_MAX_RHS columns; then
+ *   basic:        capi_dtrsm_thin(CAPI_NOTRANS, k, rb, F, ldf, 0, B, ldb) per block; capi_drow_scatter(0, k, r, n, B, ldb, jpvt, X, ldx);
+ *   minimum norm: capi_dtrsm_thin(CAPI_TRANS, k, rb, Z, ldz, 0, B, ldb) per block; rows k .. n - 1 of B <- 0;
+ *                 capi_dormqr(CAPI_LEFT, CAPI_NOTRANS, n, r, k, Z, ldz, tauz, B, ldb); capi_drow_scatter(0, n, r, n, B, ldb, jpvt, X, ldx). */
+int capi_dgelsy(capi_handle_t h, int64_t m, int64_t n, int64_t r, double* A, int64_t lda, double* tau, double* F, int64_t ldf, double* tauf, int* jpvt,
+                double* Z, int64_t ldz, double* tauz, double* B, int64_t ldb, double rcond, int min_norm, double* colnorm2, int* rank_host);
 int capi_reset_info(capi_handle_t h);
 
 /* ---- data movement: replaces serialize<> (src/matrix/serialize.hpp:12-150), the pack/unpack and
